@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — TPC-H (synthetic, dbgen-shaped) on the MI355X-native LingoDB operator runtime.
 
-  python bench.py --gpus N --steps K --warmup W [--sf 100] [--queries 1,3,…]
+  python bench.py --gpus N --steps K --warmup W [--sf 100] [--queries 1,3,…] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of all 22 TPC-H queries over the HBM-resident database, each query ending with its
 result rows handed to the host.  N > 1: launched by torch.distributed.run, one rank per GPU; the database is
@@ -9,6 +9,10 @@ sharded (orders / lineitem by order ranges, the other tables by rows; strong sca
 and every rank runs the sharded plans (lingo-db_amd/plans/tpch/dist/*.json) whose allgather / shuffle steps go
 through the library's exchange — RCCL over xGMI; torch.distributed only hands out the communicator id.
 Prints ONE JSON line on rank 0 (DESIGN.md §4 explains every field).
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds everything that takes runs of its own: the CPU baselines, the
+oracle spot checks at the bench's own scale, the steady state with replay off, the join-probe micro-benchmark and the HBM streaming ceiling (their
+keys are null / absent in a plain line).  `--dump-outputs DIR` writes the result rows of the last timed step as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -86,6 +90,45 @@ def make_comm(ctx, rank, world, dist, torch, backend):
         if comm is not None:
             comm.close()
     raise SystemExit("bench.py: no exchange transport works on every rank")
+
+
+def _as_float64(col):
+    """one column of a query result as float64: numbers as they are (decimals rounded to the nearest double), dates as days since 1970, strings
+    and fixed-size binaries as the CRC-32 of their bytes (exact in a double), NULL as NaN"""
+    import zlib
+
+    import numpy as np
+    import pyarrow as pa
+
+    typ = col.type
+    vals = col.to_pylist()
+    if pa.types.is_string(typ) or pa.types.is_large_string(typ):
+        vals = [None if v is None else zlib.crc32(v.encode()) for v in vals]
+    elif pa.types.is_binary(typ) or pa.types.is_fixed_size_binary(typ):
+        vals = [None if v is None else zlib.crc32(v) for v in vals]
+    elif pa.types.is_date(typ):
+        vals = [None if v is None else v.toordinal() - 719163 for v in vals]
+    return np.array([float("nan") if v is None else float(v) for v in vals], dtype=np.float64)
+
+
+def dump_outputs(directory, results):
+    """`--dump-outputs`: the rows the last timed step handed to the host: <directory>/q<N>_rows.npy holds the query's row count, and — for a query
+    that returned rows — <directory>/q<N>_c<i>_<column>.npy one float64 array per result column (a few thousand rows per query at most: far
+    below 64 MB; Q11 returns no row from about SF 3 on, see tpch_plans.cpu_baseline).  The database is a pure function of (--sf, --queries, seed), so two builds run with
+    the same arguments can be compared file for file."""
+    import re
+
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    for name in os.listdir(directory):  # an earlier run's arrays (a query that returned rows then and none now would leave its columns behind)
+        if re.fullmatch(r"q\d+_(rows|c\d+_\w+)\.npy", name):
+            os.remove(os.path.join(directory, name))
+    for q, table in sorted(results.items()):
+        np.save(os.path.join(directory, "q%d_rows.npy" % q), np.array([table.num_rows], dtype=np.float64))
+        for i, name in enumerate(table.schema.names if table.num_rows else []):
+            safe = re.sub(r"[^A-Za-z0-9_]+", "_", name).strip("_") or "col"
+            np.save(os.path.join(directory, "q%d_c%02d_%s.npy" % (q, i, safe)), _as_float64(table.column(i).combine_chunks()))
 
 
 def dry_run(args):
@@ -183,8 +226,16 @@ def main():
     ap.add_argument("--record-runs", type=int, default=3, help="executions per query with replay off after the timed region (per_query_record_ms); 0 = skip")
     ap.add_argument("--plans", default="files", choices=["files", "subop"], help="files: lingo-db_amd/plans/tpch/*.json (the default, the benched configuration); subop: the reference-schema sub-operator dumps "
                     "tests/golden/subop_tpch_qN.json translated by ldb_subop_translate at load time (one GPU) — the plans a LingoDB with the GPU step handler would hand over")
+    ap.add_argument("--full", action="store_true", help="also everything beside the headline figure that takes runs of its own: cpu_baseline (--cpu-sample-sf, --cpu-reference-legs), the oracle "
+                    "spot checks at the bench's own scale (--oracle-spot-check), the steady state with replay off (--record-runs), join_probe and hbm_ceiling; a plain run skips them")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps: the result rows of the last step as DIR/q<N>_c<i>_<column>.npy (float64) and DIR/q<N>_rows.npy")
     ap.add_argument("--dry-run", action="store_true", help="no device, no torch: per-rank rows / resident bytes / exchange volume of the configuration against the HBM and row-id budgets")
     args = ap.parse_args()
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        given = [a.split("=")[0] for a in sys.argv[1:] if a.split("=")[0] in ("--cpu-sample-sf", "--cpu-reference-legs", "--oracle-spot-check", "--record-runs", "--cpu-runs", "--cpu-budget-s")]
+        if given and not args.dry_run:
+            print("[bench] %s: only measured with --full; this plain run skips it" % ", ".join(given), file=sys.stderr, flush=True)
+        args.cpu_sample_sf, args.cpu_reference_legs, args.oracle_spot_check, args.record_runs = 0.0, 0, 0, 0
     if args.dry_run:
         print(json.dumps(dry_run(args)), flush=True)
         return
@@ -220,8 +271,15 @@ def main():
         else:
             dist.init_process_group(backend)
 
-    import lingodb_amd as ldb
     import tpch_plans
+
+    # a cold start compiles about a hundred kernel specialisations during the warm-up, each in a compiler process of its own: the CPUs this node gives
+    # the run (affinity mask, capped by the cgroup's quota) shared among its ranks, 16 workers per rank at most — the library's default, 8 per
+    # process whatever the host, is left as it is for other embedders
+    cpus = min(len(os.sched_getaffinity(0)), int(tpch_plans._cgroup_cpus() or 1 << 30))
+    os.environ.setdefault("LDB_JIT_THREADS", str(max(1, min(16, cpus // max(1, int(os.environ.get("LOCAL_WORLD_SIZE", world)))))))
+
+    import lingodb_amd as ldb
 
     queries = [int(q) for q in args.queries.split(",") if q] or list(range(1, 23))
     n_orders = int(round(args.sf * ORDERS_PER_SF))
@@ -262,9 +320,9 @@ def main():
         return ms.value
 
     def jit_info():
-        vals = (_C.c_int64 * 9)()
-        _capi_jit.gpu_lib().ldb_gpu_jit_info(vals, 9)
-        return dict(zip(("compiled", "memory_hits", "disk_hits", "disk_writes", "outstanding", "failed", "answered_still_compiling", "worker_threads", "taken_from_peer_processes"), [int(v) for v in vals]))
+        vals = (_C.c_int64 * 10)()
+        _capi_jit.gpu_lib().ldb_gpu_jit_info(vals, 10)
+        return dict(zip(("compiled", "memory_hits", "disk_hits", "disk_writes", "outstanding", "failed", "answered_still_compiling", "worker_threads", "taken_from_peer_processes", "compiled_in_child_processes"), [int(v) for v in vals]))
 
     first_ms = {}
     jit_wait_s = 0.0
@@ -357,6 +415,8 @@ def main():
             t = torch.tensor([record_ms[q] for q in queries], device=red_dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             record_ms = {q: float(v) for q, v in zip(queries, t.tolist())}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, results)
     per_query = {q: q_ms[q] / args.steps for q in queries}
     if world > 1:
         t = torch.tensor([per_query[q] for q in queries], device=red_dev, dtype=torch.float64)
@@ -426,8 +486,8 @@ def main():
                 if k:
                     roofline["traffic"] = round(k["fetch_bytes"] + k.get("write_raw_bytes", 0.0))
                     roofline["traffic_source"] = os.path.relpath(pmc_path, ROOT)
-        probe = runner.probe_microbench() if world == 1 and db.orders is not None and any(q in queries for q in (3, 4, 18)) else None  # needs o_orderkey, o_orderdate, l_orderkey
-        ceiling = runner.hbm_ceiling() if world == 1 else None
+        probe = runner.probe_microbench() if args.full and world == 1 and db.orders is not None and any(q in queries for q in (3, 4, 18)) else None  # needs o_orderkey, o_orderdate, l_orderkey
+        ceiling = runner.hbm_ceiling() if args.full and world == 1 else None
         # further kernels against the same HBM roofline.  Probe byte model: the COMPULSORY bytes of one launch — the probe key
         # column once (4 B per row) + the table once (every line of it is touched by a 100 % / 10 % match probe) — not
         # "key + one slot per row": with a table of range / 4 bytes (rank bitmap) or 4 B per key value (direct words) most slot
@@ -469,7 +529,7 @@ def main():
         import zlib
 
         checks = {"checksum": {"Q%d" % q: "%08x" % (zlib.crc32(repr(results[q].to_pylist()).encode()) & 0xFFFFFFFF) for q in queries if q in results}}
-        if world == 1 and 1 in results:
+        if args.full and world == 1 and 1 in results:
             from lingodb_amd import api, capi
 
             n_pass = db.lineitem.rel().scan_count([api.pred((0, db.lineitem.col("l_shipdate")), capi.F_LTE, 10471)])
@@ -567,6 +627,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "ms_per_step": round(ms_per_step, 4),
             "higher_is_better": False,
             "scaling": "strong",

@@ -159,7 +159,9 @@ int32_t ldb_gpu_jit_compile_check(char* log, int32_t cap);
  * compiles nothing.  ldb_gpu_jit_wait blocks until nothing is queued or compiling (timeout_ms < 0: no limit; *pending = still outstanding) — what a
  * benchmark calls between its first execution and its timed region.  ldb_gpu_jit_info: vals[0..9) = compiled here, in-memory hits, disk hits,
  * disk writes, outstanding, failed, calls answered "still compiling", worker threads, code objects taken over from another process that was
- * compiling the same shape (the ranks of a multi-GPU run share the work through claims in the disk cache; option jit_share_compiles). */
+ * compiling the same shape (the ranks of a multi-GPU run share the work through claims in the disk cache; option jit_share_compiles); vals[9] =
+ * compilations done in a compiler process: hiprtc serialises the compilations of one process, so each worker starts `ldb_jitc` (built beside the
+ * library) for its translation unit; option jit_child = 0, or no helper there: the worker thread compiles itself. */
 int32_t ldb_gpu_jit_wait(int64_t timeout_ms, int64_t* pending);
 int32_t ldb_gpu_jit_info(int64_t* vals, int32_t n);
 /* stop the compile workers: queued specialisations are dropped, running ones finish.  Call before the process exits (the library also registers an

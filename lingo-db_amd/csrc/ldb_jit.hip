@@ -1,7 +1,10 @@
 // ldb_jit.hip — run-time kernel specialisation with hiprtc (see ldb_jit.h).
 #include "ldb_jit.h"
 #include <hip/hiprtc.h>
+#include <dlfcn.h>
 #include <fcntl.h>
+#include <spawn.h>
+#include <sys/wait.h>
 #include <sys/stat.h>
 #include <unistd.h>
 #include <atomic>
@@ -9,6 +12,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <cstdlib>
+#include <cstring>
 #include <ctime>
 #include <deque>
 #include <memory>
@@ -17,14 +21,7 @@
 #include <unordered_map>
 
 // the kernel headers, embedded at build time (Makefile → ldb_jit_sources.inc)
-struct EmbeddedHeader {
-   const char* name;
-   const char* text;
-};
-static const EmbeddedHeader g_headers[] = {
-#include "ldb_jit_sources.inc"
-};
-static const int g_n_headers = (int) (sizeof(g_headers) / sizeof(g_headers[0]));
+#include "ldb_jit_compile.h" // the embedded kernel headers + compile(): shared with the compiler process (ldb_jitc.hip)
 
 // One entry per (device, key).  A specialisation is COMPILED on a worker thread (hiprtc takes 0.3 – 3 s per kernel; the reference answers the same
 // problem with a baseline backend that emits code in milliseconds and an optimising one behind it, include/lingodb/execution/Execution.h:103-104): the
@@ -110,63 +107,6 @@ static std::string build_source(const char* header, const char* struct_name, con
    s += ", LDB_META_BYTES);\n";
    s += kernels;
    return s;
-}
-
-// compile only (no device needed); code object into *code
-static bool compile(const std::string& src, std::vector<char>* code, std::string* err, const char* arch = "gfx950") {
-   std::vector<const char*> names, texts;
-   for (int i = 0; i < g_n_headers; i++) {
-      names.push_back(g_headers[i].name);
-      texts.push_back(g_headers[i].text);
-   }
-   hiprtcProgram prog;
-   if (hiprtcCreateProgram(&prog, src.c_str(), "ldb_spec.hip", g_n_headers, texts.data(), names.data()) != HIPRTC_SUCCESS) {
-      *err = "hiprtcCreateProgram failed";
-      return false;
-   }
-   std::vector<std::string> extra; // tuning experiments: LDB_JIT_DEFINES="-DGB_ROWS=8 -DGB_PRED_BATCH=0"
-   if (const char* defs = getenv("LDB_JIT_DEFINES")) {
-      std::string s(defs), tok;
-      for (size_t i = 0; i <= s.size(); i++) {
-         if (i == s.size() || s[i] == ' ') {
-            if (!tok.empty()) extra.push_back(tok);
-            tok.clear();
-         } else {
-            tok += s[i];
-         }
-      }
-   }
-   // The descriptor loops (LDB_UNROLL) must unroll completely or nothing folds: before unrolling
-   // their bodies hold the whole generic interpreter, which exceeds the default pragma-unroll
-   // size limit and silently leaves a generic loop reading the constexpr descriptor from memory.
-   const std::string arch_opt = std::string("--offload-arch=") + arch;
-   std::vector<const char*> opts = {arch_opt.c_str(), "-O3", "-std=c++17", "-munsafe-fp-atomics", "-mllvm", "-pragma-unroll-threshold=4000000"};
-   for (auto& e : extra) opts.push_back(e.c_str());
-   hiprtcResult r = hiprtcCompileProgram(prog, (int) opts.size(), opts.data());
-   if (r != HIPRTC_SUCCESS) {
-      size_t ls = 0;
-      hiprtcGetProgramLogSize(prog, &ls);
-      std::string log(ls, '\0');
-      if (ls) hiprtcGetProgramLog(prog, log.data());
-      *err = std::string("hiprtc: ") + hiprtcGetErrorString(r) + ": " + log.substr(0, 3000);
-      hiprtcDestroyProgram(&prog);
-      return false;
-   }
-   size_t cs = 0;
-   hiprtcGetCodeSize(prog, &cs);
-   code->resize(cs);
-   hiprtcGetCode(prog, code->data());
-   hiprtcDestroyProgram(&prog);
-   if (const char* dir = getenv("LDB_JIT_DUMP_ALL")) { // every code object, numbered (offline ISA / register-usage inspection)
-      static std::atomic<int> seq{0}; // (compilations run on several worker threads)
-      char path[512];
-      snprintf(path, sizeof(path), "%s/ldb_spec_%03d.co", dir, seq.fetch_add(1));
-      if (FILE* f = fopen(path, "wb")) {
-         fwrite(code->data(), 1, code->size(), f);
-         fclose(f);
-      }
-   }
-   return cs > 0;
 }
 
 bool ldb_jit_compile_only(const char* header, const char* struct_name, const char* kernels_src, const void* meta, size_t meta_bytes, std::string* log) {
@@ -316,13 +256,86 @@ static bool claim_or_wait(const std::string& path, std::vector<char>* code, bool
    }
    return false;
 }
+// hiprtc serialises the compilations of one process (six worker threads finish six kernels no sooner than one thread does), so a worker hands its
+// translation unit to a compiler PROCESS — ldb_jitc, built beside the library: same embedded headers, same compile() — and the workers' compilations
+// really run side by side: a cold start of the 22 TPC-H plans compiles its hundred-odd kernels in a fraction of the time.  The child never needs a
+// device (it is started with the GPUs hidden).  Option jit_child = 0 (LDB_JIT_CHILD=0), a missing helper or a failed start: compile in this thread
+// (ldb_gpu_jit_info vals[9] counts the compilations that did run in a child).
+extern char** environ;
+static std::string helper_path() {
+   static const std::string path = [] {
+      Dl_info info;
+      if (!dladdr((void*) &ldb_gpu_jit_shutdown, &info) || !info.dli_fname) return std::string();
+      std::string p(info.dli_fname);
+      const size_t slash = p.rfind('/');
+      p = (slash == std::string::npos ? std::string(".") : p.substr(0, slash)) + "/ldb_jitc";
+      return access(p.c_str(), X_OK) == 0 ? p : std::string();
+   }();
+   return path;
+}
+static std::atomic<int64_t> g_child_compiles{0}; // code objects that came from a compiler process (ldb_gpu_jit_info vals[9])
+// CHILD_UNAVAILABLE: nothing was compiled (switched off, no helper, it could not be started or died): the caller compiles in its own thread;
+// CHILD_COMPILE_ERROR: the compiler itself refused the translation unit, *err holds its log — compiling again would only repeat that
+enum ChildResult { CHILD_OK, CHILD_COMPILE_ERROR, CHILD_UNAVAILABLE };
+static ChildResult compile_in_child(const JitJob& job, std::vector<char>* code, std::string* err) {
+   if (ldb_option("jit_child", 1) == 0 || getenv("LDB_JIT_DUMP_ALL") || helper_path().empty()) return CHILD_UNAVAILABLE;
+   // source, code object and log pass through a directory of this job's own (mkdtemp: a fresh name, mode 0700): nothing is opened under a name another
+   // user of the host could have prepared
+   const char* tmp = getenv("TMPDIR");
+   std::string dir = std::string(tmp && *tmp ? tmp : "/tmp") + "/ldb_jitc_XXXXXX";
+   if (!mkdtemp(dir.data())) return CHILD_UNAVAILABLE;
+   const std::string src = dir + "/unit.hip", out = dir + "/unit.co", log = dir + "/unit.log";
+   ChildResult res = CHILD_UNAVAILABLE;
+   bool ok = false;
+   if (FILE* f = fopen(src.c_str(), "wb")) {
+      ok = fwrite(job.src.data(), 1, job.src.size(), f) == job.src.size();
+      ok = fclose(f) == 0 && ok;
+   }
+   if (ok) {
+      std::vector<char*> env;
+      for (char** e = environ; e && *e; e++)
+         if (strncmp(*e, "HIP_VISIBLE_DEVICES=", 20) != 0) env.push_back(*e);
+      char hide[] = "HIP_VISIBLE_DEVICES=-1";
+      env.push_back(hide);
+      env.push_back(nullptr);
+      const std::string helper = helper_path();
+      char* argv[] = {(char*) helper.c_str(), (char*) src.c_str(), (char*) job.arch.c_str(), (char*) out.c_str(), (char*) log.c_str(), nullptr};
+      pid_t pid = 0;
+      int status = -1;
+      if (posix_spawn(&pid, helper.c_str(), nullptr, nullptr, argv, env.data()) == 0) {
+         while (waitpid(pid, &status, 0) < 0 && errno == EINTR) {}
+         if (WIFEXITED(status) && WEXITSTATUS(status) == 0 && disk_read(out, code)) {
+            res = CHILD_OK;
+            g_child_compiles.fetch_add(1);
+         } else if (WIFEXITED(status) && WEXITSTATUS(status) == 1) { // ldb_jitc: hiprtc refused the unit, its log is in `log`
+            res = CHILD_COMPILE_ERROR;
+            if (FILE* f = fopen(log.c_str(), "rb")) {
+               char buf[3200];
+               const size_t n = fread(buf, 1, sizeof(buf), f);
+               fclose(f);
+               err->assign(buf, n);
+            }
+            if (err->empty()) *err = "hiprtc: the compiler process reported an error without a log";
+         }
+      }
+   }
+   unlink(src.c_str());
+   unlink(out.c_str());
+   unlink(log.c_str());
+   rmdir(dir.c_str());
+   return res;
+}
 static void run_job(JitJob& job) {
    auto t0 = std::chrono::steady_clock::now();
    std::vector<char> code;
    std::string err;
    bool claimed = false;
    const bool from_peer = claim_or_wait(job.disk_path, &code, &claimed);
-   const bool ok = from_peer || compile(job.src, &code, &err, job.arch.c_str());
+   bool ok = from_peer;
+   if (!from_peer) {
+      const ChildResult child = compile_in_child(job, &code, &err);
+      ok = child == CHILD_OK || (child == CHILD_UNAVAILABLE && compile(job.src, &code, &err, job.arch.c_str()));
+   }
    const double ms = from_peer ? 0.0 : std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
    bool wrote = false;
    if (from_peer) g_shared_from_peers.fetch_add(1);
@@ -532,12 +545,14 @@ extern "C" int32_t ldb_gpu_jit_wait(int64_t timeout_ms, int64_t* pending) {
    return LDB_OK;
 }
 // vals[0..n): kernels compiled in this process, in-memory hits, code objects taken from the disk cache, written to it, compilations outstanding,
-// failed, calls answered "still compiling" (the caller ran its generic kernel), worker threads
+// failed, calls answered "still compiling" (the caller ran its generic kernel), worker threads, code objects taken over from a peer process,
+// compilations done in a compiler process (ldb_jitc) instead of a worker thread
 extern "C" int32_t ldb_gpu_jit_info(int64_t* vals, int32_t n) {
    if (!vals || n < 0) LDB_FAIL(LDB_ERR_INVALID, "jit_info: NULL argument");
    std::lock_guard<std::mutex> lock(g_mu);
-   const int64_t all[9] = {g_compiled, g_hits, g_disk_hits, g_disk_writes, (int64_t) g_queue.size() + g_running, g_failed, g_async_misses, (int64_t) g_workers, g_shared_from_peers.load()};
-   for (int32_t i = 0; i < n; i++) vals[i] = i < 9 ? all[i] : 0;
+   const int64_t all[10] = {g_compiled, g_hits, g_disk_hits, g_disk_writes, (int64_t) g_queue.size() + g_running, g_failed, g_async_misses, (int64_t) g_workers, g_shared_from_peers.load(),
+                            g_child_compiles.load()};
+   for (int32_t i = 0; i < n; i++) vals[i] = i < 10 ? all[i] : 0;
    return LDB_OK;
 }
 

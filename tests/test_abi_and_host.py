@@ -203,6 +203,41 @@ def test_jit_compiles_in_the_background_and_caches_code_objects_on_disk(tmp_path
     assert r3.returncode == 0 and "disk cache is disabled" in r3.stdout and not os.path.exists(str(tmp_path / "off")), r3.stdout + r3.stderr
 
 
+def test_jit_compiles_in_a_compiler_process_and_gets_the_same_code_object(tmp_path):
+    """hiprtc serialises the compilations of one process, so a compile worker hands its translation unit to `ldb_jitc` (built beside the library: the
+    same embedded headers, the same compile()).  With the helper there the compilation is counted as done in a child (ldb_gpu_jit_info vals[9]);
+    with LDB_JIT_CHILD=0 the worker thread compiles itself and the counter stays 0; the code object in the disk cache has the same name and the
+    same bytes on both paths.  A unit hiprtc refuses is reported once, with the compiler's log, by the child alone.  Device-less."""
+    import subprocess
+    import sys
+
+    assert os.access(os.path.join(ROOT, "lingo-db_amd", "ldb_jitc"), os.X_OK), "ldb_jitc was not built beside liblingodb_gpu.so"
+    code = ("import ctypes as C, sys; sys.path.insert(0, %r); from lingodb_amd import capi; lib = capi.gpu_lib(); buf = C.create_string_buffer(4000);"
+            "st = lib.ldb_gpu_jit_cache_selftest(buf, 4000); v = (C.c_int64 * 10)(); lib.ldb_gpu_jit_info(v, 10); print(st, list(v), buf.value.decode())") % os.path.join(ROOT, "lingo-db_amd")
+
+    def run(d, **extra):
+        r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, LDB_JIT_CACHE_DIR=str(d), LDB_JIT_ASYNC="1", TMPDIR=str(tmp_path), **extra),
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0 and r.stdout.startswith("0 "), r.stdout + r.stderr
+        info = eval(r.stdout.split(" ", 1)[1].split("]")[0] + "]")
+        files = sorted(os.path.join(p, f) for p, _, fs in os.walk(str(d)) for f in fs)
+        assert len(files) == 1
+        with open(files[0], "rb") as f:
+            return info, os.path.relpath(files[0], str(d)), f.read()
+
+    info_child, name_child, code_child = run(tmp_path / "child")
+    info_thread, name_thread, code_thread = run(tmp_path / "thread", LDB_JIT_CHILD="0")
+    assert info_child[9] == 1 and info_child[3] == 1 and info_child[5] == 0, info_child
+    assert info_thread[9] == 0 and info_thread[3] == 1 and info_thread[5] == 0, info_thread
+    assert name_child == name_thread and code_child == code_thread and code_child[:4] == b"\x7fELF"
+    assert not [n for n in os.listdir(str(tmp_path)) if n.startswith("ldb_jitc_")], "the compiler process's exchange directory was left behind"
+    # the helper's own verdict on a unit that does not compile: exit status 1 and the compiler's log, nothing else written
+    bad = tmp_path / "bad.hip"
+    bad.write_text("#include \"ldb_gb_kernel.h\"\nthis is not C++;\n")
+    r = subprocess.run([os.path.join(ROOT, "lingo-db_amd", "ldb_jitc"), str(bad), "gfx950", str(tmp_path / "bad.co"), str(tmp_path / "bad.log")], capture_output=True, timeout=600)
+    assert r.returncode == 1 and not os.path.exists(str(tmp_path / "bad.co")) and "error" in (tmp_path / "bad.log").read_text()
+
+
 def test_processes_sharing_a_jit_cache_compile_a_shape_once(tmp_path):
     """round 6: the ranks of a multi-GPU run meet the same kernel shapes at the same time and share one disk cache — a worker claims a shape
     (`<hash>.co.lock`) before compiling it, a worker of another process that finds the claim waits for the code object instead of compiling it again;

@@ -315,3 +315,36 @@ def test_no_base_table_probes_a_non_unique_table_of_its_own_primary_key():
                     b = builds[s["ht"]]
                     if not b.get("unique", False) and s["in"] in base and s["keys"] == [primary[base[s["in"]]]]:
                         assert (q, s["keys"][0]) in allowed, (sub or "single", q, s)
+
+
+def test_bench_dump_outputs_encoding(tmp_path):
+    """`bench.py --dump-outputs`: one float64 array per result column — decimals as their value, dates as days since 1970, strings and binaries as the
+    CRC-32 of their bytes, NULL as NaN — and the row count of every query; a query without rows writes its row count only, and a second dump into
+    the same directory leaves nothing of the first behind"""
+    import datetime
+    import decimal
+    import sys
+    import zlib
+
+    import numpy as np
+    import pyarrow as pa
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    t = pa.table({"sum qty": pa.array([decimal.Decimal("1.25"), None], pa.decimal128(38, 2)), "name": pa.array(["ab", None]), "day": pa.array([datetime.date(1998, 9, 2), None], pa.date32()),
+                  "flag": pa.array([b"A\0\0\0", b"B\0\0\0"], pa.binary(4)), "n": pa.array([1, 2], pa.int64())})
+    out = str(tmp_path / "dump")
+    bench.dump_outputs(out, {1: t, 11: t.slice(0, 0)})
+    assert sorted(os.listdir(out)) == ["q11_rows.npy", "q1_c00_sum_qty.npy", "q1_c01_name.npy", "q1_c02_day.npy", "q1_c03_flag.npy", "q1_c04_n.npy", "q1_rows.npy"]
+    load = lambda n: np.load(os.path.join(out, n))
+    assert all(load(n).dtype == np.float64 for n in os.listdir(out))
+    assert load("q1_rows.npy").tolist() == [2.0] and load("q11_rows.npy").tolist() == [0.0]
+    assert load("q1_c00_sum_qty.npy")[0] == 1.25 and np.isnan(load("q1_c00_sum_qty.npy")[1])
+    assert load("q1_c01_name.npy")[0] == float(zlib.crc32(b"ab")) and np.isnan(load("q1_c01_name.npy")[1])
+    assert load("q1_c02_day.npy")[0] == 10471.0 and np.isnan(load("q1_c02_day.npy")[1])
+    assert load("q1_c03_flag.npy").tolist() == [float(zlib.crc32(b"A\0\0\0")), float(zlib.crc32(b"B\0\0\0"))]
+    assert load("q1_c04_n.npy").tolist() == [1.0, 2.0]
+    open(os.path.join(out, "notes.txt"), "w").close()  # not a dump file: stays
+    bench.dump_outputs(out, {1: t.slice(0, 0)})
+    assert sorted(os.listdir(out)) == ["notes.txt", "q1_rows.npy"]

@@ -8,7 +8,7 @@ runs, as MI355X_MICROARCH.md prescribes), calibrated on kernels whose byte count
 rocprofv3 reports FETCH_SIZE / WRITE_SIZE in KiB; on gfx950 FETCH_SIZE under-reports streaming
 reads (½ for 16 B/lane loads; other widths "uncalibrated"), so the factor is measured, not
 assumed: calib = known bytes of a calibration launch / its raw FETCH_SIZE.  The calibration
-launches are bench.py's hbm_ceiling() scans — the library's count-only scan over one dense column
+launches are the hbm_ceiling() scans of `bench.py --full` — the library's count-only scan over one dense column
 (every cache line of the column is fetched exactly once): a 16-byte decimal column read with
 8-byte loads (bytes = rows x 16) and a 4-byte date column read with dword loads (rows x 4).  The
 launches of the calibration kernel are clustered by raw value and matched to --calib-bytes in
