@@ -410,9 +410,18 @@ int32_t ldb_gpu_map_muldiv(ldb_ctx* ctx, ldb_rel* in, ldb_colref num, int64_t mu
  * fixed the scales (casts = MUL_POW10 / SDIV_POW10, sql_analyzer.cpp:3058-3159), comparisons
  * (:374-466), CASE (scf.if on db.derive_truth) and NULL handling.  Arithmetic and comparisons yield
  * NULL when an operand is NULL; AND / OR are three-valued; SDIV by zero yields NULL.
- * out_type: INT32 / INT64 / DATE32 / DECIMAL128(p, s) / BOOL8. */
+ * Floats: a FLOAT32 / FLOAT64 column, LDB_X_FCONST, LDB_X_I2F and LDB_X_FCVT push an f32 / f64 slot; the F* instructions
+ * compute on such slots as arith.addf / subf / mulf / divf (LowerToStd.cpp:1593-1596; two operands of ONE width, no fused
+ * multiply-add, division by zero is IEEE ±inf / NaN and not NULL) and compare them with the ORDERED predicates
+ * (translateFPredicate, :870-895: any NaN operand gives false, NEQ included); the casts are CastOpLowering's sitofp /
+ * fptosi / extf / truncf (:947-1018).  SELECT / COALESCE take two value operands of one class and width; ISNULL, AND, OR,
+ * NOT and ROW are unchanged.  The program is type-checked on the host (every slot is an integer, a bool, an f32 or an
+ * f64): a float under an integer instruction or the reverse, mixed widths, an `arg` that is not 32 / 64, or a result whose
+ * class does not match out_type is LDB_ERR_INVALID with the instruction index.
+ * out_type: INT32 / INT64 / DATE32 / DECIMAL128(p, s) / BOOL8 for an integer result, FLOAT32 / FLOAT64 for a float result
+ * of that width. */
 typedef enum {
-   LDB_X_COL = 0, /* push column `col` (integer, decimal, date, char(1), bool) */
+   LDB_X_COL = 0, /* push column `col` (integer, decimal, date, char(1), bool; float32 / float64: a float slot of that width) */
    LDB_X_CONST = 1, /* push the 128-bit constant (lo, hi) */
    LDB_X_ADD = 2,
    LDB_X_SUB = 3, /* a b → a - b */
@@ -428,8 +437,18 @@ typedef enum {
    LDB_X_SELECT = 13, /* c a b → (c is true) ? a : b */
    LDB_X_ISNULL = 14,
    LDB_X_COALESCE = 15, /* a b → a unless NULL, then b */
-   LDB_X_ROW = 16 /* push the LOGICAL row number of the relation (0 … n-1): the identity of a tuple of the outer stream when a
-                     nested_map's inner pipeline is reduced per outer tuple (subop.nested_map, SubOpToControlFlow.cpp:1204-1250) */
+   LDB_X_ROW = 16, /* push the LOGICAL row number of the relation (0 … n-1): the identity of a tuple of the outer stream when a
+                      nested_map's inner pipeline is reduced per outer tuple (subop.nested_map, SubOpToControlFlow.cpp:1204-1250) */
+   LDB_X_FCONST = 17, /* push a float: lo = IEEE-754 bits of an f64 value, arg = 32 / 64 = the slot's width (32: the value
+                         converted to f32, round-to-nearest-even) */
+   LDB_X_FADD = 18, /* a b → a + b (arith.addf); both operands float and of the same width, also for FSUB / FMUL / FDIV */
+   LDB_X_FSUB = 19,
+   LDB_X_FMUL = 20,
+   LDB_X_FDIV = 21, /* IEEE: division by zero gives ±inf / NaN, not NULL */
+   LDB_X_FCMP = 22, /* a b → bool, arg = ldb_filter_op (EQ .. GTE), ordered: false when an operand is NaN (NEQ too) */
+   LDB_X_I2F = 23, /* i → f, arg = 32 / 64: sitofp of the (up to 128-bit) integer slot with one rounding, to nearest even */
+   LDB_X_F2I = 24, /* f → i64: fptosi (towards zero); NaN or a value outside [-2^63, 2^63) gives NULL */
+   LDB_X_FCVT = 25 /* f → f, arg = 32 / 64: arith.extf / arith.truncf */
 } ldb_xop;
 typedef struct {
    int32_t op; /* ldb_xop */

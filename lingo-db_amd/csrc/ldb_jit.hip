@@ -666,6 +666,7 @@ extern "C" int32_t ldb_gpu_jit_compile_check(char* log, int32_t cap) {
    if (ok) ok = ldb_scan_jit_check(&err);
    if (ok) ok = ldb_join_jit_check(&err);
    if (ok) ok = ldb_expr_jit_check(&err);
+   if (ok) ok = ldb_fexpr_jit_check(&err);
    if (log && cap > 0) snprintf(log, (size_t) cap, "%s", err.c_str());
    if (ok) {
       if (const char* dump = getenv("LDB_JIT_DUMP")) { // code object for llvm-objdump inspection

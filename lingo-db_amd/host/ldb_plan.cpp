@@ -45,9 +45,10 @@ struct Value {
    ldb_rel* lazyRel = nullptr; // TABLE used as a relation
 };
 
-struct Scalar { // expression type: integer (p = 0) or decimal(p, s), date, bool
-   enum Kind { INT, DEC, DATE, BOOL } kind = INT;
+struct Scalar { // expression type: integer (p = 0) or decimal(p, s), date, bool, f32 / f64
+   enum Kind { INT, DEC, DATE, BOOL, F32, F64 } kind = INT;
    int32_t p = 0, s = 0;
+   bool isFloat() const { return kind == F32 || kind == F64; }
 };
 
 struct Interp {
@@ -354,6 +355,8 @@ struct Interp {
          case LDB_T_INT32:
          case LDB_T_INT64:
          case LDB_T_CHAR4: s.kind = Scalar::INT; break;
+         case LDB_T_FLOAT32: s.kind = Scalar::F32; break;
+         case LDB_T_FLOAT64: s.kind = Scalar::F64; break;
          default: throw std::runtime_error("plan: expression over a non-numeric column");
       }
       return s;
@@ -398,6 +401,47 @@ struct Interp {
       if (to.s > fs) b.push(LDB_X_MUL_POW10, to.s - fs);
       else if (to.s < fs) b.push(LDB_X_SDIV_POW10, fs - to.s);
    }
+   // ---- floats (the plan is post-frontend: the reference has inserted db.cast, so both sides of an operator have ONE type)
+   static Scalar floatScalar(int bits) {
+      Scalar s;
+      s.kind = bits == 32 ? Scalar::F32 : Scalar::F64;
+      return s;
+   }
+   static int32_t floatBits(const Scalar& s) { return s.kind == Scalar::F32 ? 32 : 64; }
+   static const char* scalarName(const Scalar& s) {
+      switch (s.kind) {
+         case Scalar::F32: return "f32";
+         case Scalar::F64: return "f64";
+         case Scalar::DEC: return "decimal";
+         case Scalar::DATE: return "date";
+         case Scalar::BOOL: return "bool";
+         default: return "integer";
+      }
+   }
+   // true: a float operator (both sides floats of one width); false: no float involved; anything else needs a cast
+   static bool floatPair(const std::string& op, const Scalar& l, const Scalar& r) {
+      if (!l.isFloat() && !r.isFloat()) return false;
+      if (l.kind != r.kind)
+         throw std::runtime_error("plan: '" + op + "' over " + scalarName(l) + " and " + scalarName(r) + ": floats do not mix with other types or widths, add an explicit cast ({\"cast\": [\"" +
+                                  (l.isFloat() ? scalarName(l) : scalarName(r)) + "\", …]})");
+      return true;
+   }
+   static void pushFConst(XB& b, double v, int32_t bits) {
+      int64_t raw;
+      memcpy(&raw, &v, 8);
+      b.push(LDB_X_FCONST, bits, {0, 0}, (__int128) (uint64_t) raw);
+   }
+   // CastOpLowering's decimal scale factor: single-precision powf widened to the target type (LowerToStd.cpp:947-1018)
+   static double castPow10(int32_t s) { return (double) powf(10.0f, (float) s); }
+   static Scalar parseCastType(const std::string& t) {
+      if (t == "f32") return floatScalar(32);
+      if (t == "f64") return floatScalar(64);
+      if (t == "i64") return Scalar{};
+      int p = 0, sc = 0;
+      char tail = 0;
+      if (sscanf(t.c_str(), "decimal(%d,%d%c", &p, &sc, &tail) == 3 && tail == ')' && p >= 1 && p <= 38 && sc >= 0 && sc <= p) return decScalar({p, sc});
+      throw std::runtime_error("plan: cast target '" + t + "' (f32, f64, i64 or decimal(p,s) expected)");
+   }
    // compile an expression tree into postfix code; returns its type
    Scalar compileX(const std::vector<const ldb_table*>& sides, const J& e, XB& b) {
       if (e.kind == J::NUM) {
@@ -426,6 +470,12 @@ struct Interp {
          arity(2);
          XB lb, rb;
          const Scalar l = compileX(sides, args.arr[0], lb), r = compileX(sides, args.arr[1], rb);
+         if (floatPair(op, l, r)) { // arith.addf / subf
+            b.ins.insert(b.ins.end(), lb.ins.begin(), lb.ins.end());
+            b.ins.insert(b.ins.end(), rb.ins.begin(), rb.ins.end());
+            b.push(op == "add" ? LDB_X_FADD : LDB_X_FSUB);
+            return l;
+         }
          if (l.kind == Scalar::INT && r.kind == Scalar::INT) {
             b.ins.insert(b.ins.end(), lb.ins.begin(), lb.ins.end());
             b.ins.insert(b.ins.end(), rb.ins.begin(), rb.ins.end());
@@ -444,6 +494,10 @@ struct Interp {
          arity(2);
          const Scalar l = compileX(sides, args.arr[0], b);
          const Scalar r = compileX(sides, args.arr[1], b);
+         if (floatPair(op, l, r)) { // arith.mulf
+            b.push(LDB_X_FMUL);
+            return l;
+         }
          b.push(LDB_X_MUL);
          if (l.kind == Scalar::INT && r.kind == Scalar::INT) return Scalar{};
          const DecimalType dl = asDec(l), dr = asDec(r), t = typeAfterMul(dl, dr); // DecimalMulOpLowering (LowerToStd.cpp:653-677)
@@ -455,6 +509,11 @@ struct Interp {
          const Scalar l = compileX(sides, args.arr[0], b);
          XB rb;
          const Scalar r = compileX(sides, args.arr[1], rb);
+         if (floatPair(op, l, r)) { // arith.divf: IEEE, x / 0 = ±inf / NaN
+            b.ins.insert(b.ins.end(), rb.ins.begin(), rb.ins.end());
+            b.push(LDB_X_FDIV);
+            return l;
+         }
          const DecimalType dl = asDec(l), dr = asDec(r), t = typeAfterDiv(dl, dr); // DecimalOpScaledLowering (LowerToStd.cpp:631-651)
          const int32_t k = t.s + dr.s - dl.s;
          if (k < 0) throw std::runtime_error("plan: decimal division with a negative scale adjustment");
@@ -467,7 +526,7 @@ struct Interp {
          arity(2);
          const Scalar l = compileX(sides, args.arr[0], b);
          const Scalar r = compileX(sides, args.arr[1], b);
-         if (l.kind != Scalar::INT || r.kind != Scalar::INT) throw std::runtime_error("plan: idiv takes two integers (decimals divide with 'div')");
+         if (l.kind != Scalar::INT || r.kind != Scalar::INT) throw std::runtime_error("plan: idiv takes two integers (decimals and floats divide with 'div')");
          b.push(LDB_X_SDIV);
          return Scalar{};
       }
@@ -483,7 +542,8 @@ struct Interp {
          XB lb, rb;
          const Scalar l = compileX(sides, args.arr[1], lb), r = compileX(sides, args.arr[2], rb);
          b.ins.insert(b.ins.end(), lb.ins.begin(), lb.ins.end());
-         if (l.kind == Scalar::DEC || r.kind == Scalar::DEC) {
+         const bool flt = floatPair(op, l, r); // arith.cmpf, ordered predicates
+         if (!flt && (l.kind == Scalar::DEC || r.kind == Scalar::DEC)) {
             const DecimalType t = higherDecimalType(asDec(l), asDec(r));
             castTo(b, l, t);
             b.ins.insert(b.ins.end(), rb.ins.begin(), rb.ins.end());
@@ -491,7 +551,7 @@ struct Interp {
          } else {
             b.ins.insert(b.ins.end(), rb.ins.begin(), rb.ins.end());
          }
-         b.push(LDB_X_CMP, cmp);
+         b.push(flt ? LDB_X_FCMP : LDB_X_CMP, cmp);
          Scalar s;
          s.kind = Scalar::BOOL;
          return s;
@@ -521,7 +581,7 @@ struct Interp {
          const Scalar l = compileX(sides, args.arr[isCase ? 1 : 0], lb), r = compileX(sides, args.arr[isCase ? 2 : 1], rb);
          Scalar out = l;
          b.ins.insert(b.ins.end(), lb.ins.begin(), lb.ins.end());
-         if (l.kind == Scalar::DEC || r.kind == Scalar::DEC) {
+         if (!floatPair(op, l, r) && (l.kind == Scalar::DEC || r.kind == Scalar::DEC)) {
             const DecimalType t = higherDecimalType(asDec(l), asDec(r));
             castTo(b, l, t);
             b.ins.insert(b.ins.end(), rb.ins.begin(), rb.ins.end());
@@ -536,8 +596,44 @@ struct Interp {
       if (op == "neg") {
          arity(1);
          const Scalar t = compileX(sides, args.arr[0], b);
+         if (t.isFloat()) throw std::runtime_error("plan: neg of a float is not built");
          b.push(LDB_X_NEG);
          return t;
+      }
+      if (op == "f32" || op == "f64") { // float literal: {"f64": "0.85"}
+         if (args.kind != J::STR) throw std::runtime_error("plan: a float literal is written {\"" + op + "\": \"0.85\"}");
+         char* end = nullptr;
+         const double v = strtod(args.str.c_str(), &end);
+         if (args.str.empty() || *end) throw std::runtime_error("plan: float literal '" + args.str + "'");
+         pushFConst(b, v, op == "f32" ? 32 : 64);
+         return floatScalar(op == "f32" ? 32 : 64);
+      }
+      if (op == "cast") { // {"cast": [T, e]}: db.cast with a float on one side (CastOpLowering, LowerToStd.cpp:947-1018)
+         arity(2);
+         if (args.arr[0].kind != J::STR) throw std::runtime_error("plan: cast takes [type, expression]");
+         const Scalar to = parseCastType(args.arr[0].str);
+         const Scalar from = compileX(sides, args.arr[1], b);
+         if (to.isFloat() && from.isFloat()) {
+            if (to.kind != from.kind) b.push(LDB_X_FCVT, floatBits(to)); // arith.extf / truncf
+            return to;
+         }
+         if (to.isFloat()) { // sitofp; a decimal then divides by (T) powf(10, s)
+            b.push(LDB_X_I2F, floatBits(to));
+            if (from.kind == Scalar::DEC && from.s > 0) {
+               pushFConst(b, castPow10(from.s), floatBits(to));
+               b.push(LDB_X_FDIV);
+            }
+            return to;
+         }
+         if (from.isFloat()) { // fptosi; a decimal target first multiplies by (T) powf(10, s)
+            if (to.kind == Scalar::DEC && to.s > 0) {
+               pushFConst(b, castPow10(to.s), floatBits(from));
+               b.push(LDB_X_FMUL);
+            }
+            b.push(LDB_X_F2I);
+            return to;
+         }
+         throw std::runtime_error("plan: cast from " + std::string(scalarName(from)) + " to " + args.arr[0].str + ": only casts with a float on one side are built");
       }
       throw std::runtime_error("plan: unknown expression operator '" + op + "'");
    }
@@ -571,6 +667,7 @@ struct Interp {
          f.isCol = true;
          f.col = resolve(sides, e.str, "aggregate");
          f.type = scalarOfCol(typeOf(sides, f.col));
+         if (f.type.isFloat()) throw std::runtime_error("plan: aggregate over a float column is not built in the plan language");
          return f;
       }
       if (e.kind == J::OBJ && e.obj.size() == 1 && (e.obj[0].first == "add" || e.obj[0].first == "sub")) { // (k ± col)
@@ -579,6 +676,7 @@ struct Interp {
             f.constPlus = true;
             f.col = resolve(sides, a.arr[1].str, "aggregate");
             const Scalar ct = scalarOfCol(typeOf(sides, f.col));
+            if (ct.isFloat()) throw std::runtime_error("plan: aggregate over a float column is not built in the plan language");
             f.sign = e.obj[0].first == "add" ? 1 : -1;
             if (ct.kind == Scalar::DEC) { // int literal → decimal(19,0) → common scale of the column (sql_analyzer.cpp:3125-3141)
                f.type = decScalar(higherDecimalType({19, 0}, {ct.p, ct.s}));
@@ -945,6 +1043,8 @@ struct Interp {
             if (ty.kind == Scalar::DEC) ct = {LDB_T_DECIMAL128, ty.p, ty.s, 1};
             else if (ty.kind == Scalar::BOOL) ct = {LDB_T_BOOL8, 0, 0, 1};
             else if (ty.kind == Scalar::DATE) ct = {LDB_T_DATE32, 0, 0, 1};
+            else if (ty.kind == Scalar::F32) ct = {LDB_T_FLOAT32, 0, 0, 1};
+            else if (ty.kind == Scalar::F64) ct = {LDB_T_FLOAT64, 0, 0, 1};
             check(ldb_gpu_map_expr(ctx, in, b.ins.data(), (int32_t) b.ins.size(), ct, as.c_str(), &t), "map expr");
          }
          hidden.push_back(t);

@@ -1,6 +1,7 @@
 """Thin object layer over the C-ABI (tests / bench harness).  Every call goes through
 liblingodb_gpu.so; nothing here computes query results on the CPU."""
 import ctypes as C
+import struct
 
 import numpy as np
 import pyarrow as pa
@@ -234,6 +235,30 @@ class Table:
         return pa.Table.from_batches([batch])
 
 
+def encode_xprog(prog):
+    """postfix list of ("col", (side, col)) | ("const", int) | ("add",) … | ("cmp", F_op) | ("mul10", k) | ("div10", k) |
+    ("fconst", value, 32|64) | ("fadd",) ("fsub",) ("fmul",) ("fdiv",) | ("fcmp", F_op) | ("i2f", 32|64) | ("f2i",) | ("fcvt", 32|64)
+    → the ldb_xinstr array of ldb_gpu_map_expr (no context needed)"""
+    ops = {"add": capi.X_ADD, "sub": capi.X_SUB, "mul": capi.X_MUL, "sdiv": capi.X_SDIV, "neg": capi.X_NEG, "and": capi.X_AND, "or": capi.X_OR, "not": capi.X_NOT,
+           "select": capi.X_SELECT, "isnull": capi.X_ISNULL, "coalesce": capi.X_COALESCE, "row": capi.X_ROW,
+           "fadd": capi.X_FADD, "fsub": capi.X_FSUB, "fmul": capi.X_FMUL, "fdiv": capi.X_FDIV, "f2i": capi.X_F2I}
+    with_arg = {"cmp": capi.X_CMP, "mul10": capi.X_MUL_POW10, "div10": capi.X_SDIV_POW10, "fcmp": capi.X_FCMP, "i2f": capi.X_I2F, "fcvt": capi.X_FCVT}
+    arr = (capi.XInstr * len(prog))()
+    for i, ins in enumerate(prog):
+        if ins[0] == "col":
+            arr[i].op, arr[i].col = capi.X_COL, colref(*ins[1])
+        elif ins[0] == "const":
+            lo, hi = _split128(ins[1])
+            arr[i].op, arr[i].lo, arr[i].hi = capi.X_CONST, lo if lo < 1 << 63 else lo - (1 << 64), hi
+        elif ins[0] == "fconst":  # lo = the bits of the value as an f64; the library rounds it to f32 for a 32-bit slot
+            arr[i].op, arr[i].arg, arr[i].lo = capi.X_FCONST, ins[2], struct.unpack("<q", struct.pack("<d", float(ins[1])))[0]
+        elif ins[0] in with_arg:
+            arr[i].op, arr[i].arg = with_arg[ins[0]], ins[1]
+        else:
+            arr[i].op = ops[ins[0]]
+    return arr
+
+
 class Rel:
     def __init__(self, ctx, handle, deps=()):
         self.ctx, self.h = ctx, handle
@@ -293,22 +318,8 @@ class Rel:
         return Rel(self.ctx, r, self.deps)
 
     def map_expr(self, prog, out_type=capi.T_INT64, p=0, s=0, name="expr"):
-        """prog: postfix list of ("col", (side, col)) | ("const", int) | ("add",) … | ("cmp", F_op) | ("mul10", k) | ("div10", k)"""
-        ops = {"add": capi.X_ADD, "sub": capi.X_SUB, "mul": capi.X_MUL, "sdiv": capi.X_SDIV, "neg": capi.X_NEG, "and": capi.X_AND, "or": capi.X_OR, "not": capi.X_NOT,
-               "select": capi.X_SELECT, "isnull": capi.X_ISNULL, "coalesce": capi.X_COALESCE}
-        arr = (capi.XInstr * len(prog))()
-        for i, ins in enumerate(prog):
-            if ins[0] == "col":
-                arr[i].op, arr[i].col = capi.X_COL, colref(*ins[1])
-            elif ins[0] == "const":
-                lo, hi = _split128(ins[1])
-                arr[i].op, arr[i].lo, arr[i].hi = capi.X_CONST, lo if lo < 1 << 63 else lo - (1 << 64), hi
-            elif ins[0] == "cmp":
-                arr[i].op, arr[i].arg = capi.X_CMP, ins[1]
-            elif ins[0] in ("mul10", "div10"):
-                arr[i].op, arr[i].arg = (capi.X_MUL_POW10 if ins[0] == "mul10" else capi.X_SDIV_POW10), ins[1]
-            else:
-                arr[i].op = ops[ins[0]]
+        """prog: postfix list, see encode_xprog; out_type T_FLOAT32 / T_FLOAT64 for a float result"""
+        arr = encode_xprog(prog)
         t = C.c_void_p()
         check(self.ctx.lib.ldb_gpu_map_expr(self.ctx.h, self.h, arr, len(prog), ColType(out_type, p, s, 1), name.encode(), C.byref(t)))
         return Table(self.ctx, t)

@@ -110,6 +110,7 @@ class XInstr(C.Structure):
 
 
 X_COL, X_CONST, X_ADD, X_SUB, X_MUL, X_SDIV, X_MUL_POW10, X_SDIV_POW10, X_NEG, X_CMP, X_AND, X_OR, X_NOT, X_SELECT, X_ISNULL, X_COALESCE, X_ROW = range(17)
+X_FCONST, X_FADD, X_FSUB, X_FMUL, X_FDIV, X_FCMP, X_I2F, X_F2I, X_FCVT = range(17, 26)
 
 
 class CommStats(C.Structure):
