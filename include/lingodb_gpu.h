@@ -171,7 +171,7 @@ int32_t ldb_gpu_jit_shutdown(void);
 int32_t ldb_gpu_jit_cache_selftest(char* log, int32_t cap);
 
 /* Process-wide tuning options (each also readable from the environment as LDB_<NAME> on first use):
- *   jit (0/1), jit_min_rows      — run-time kernel specialisation and its row threshold (default 4 M)
+ *   jit (0/1), jit_min_rows      — run-time kernel specialisation and its row threshold (default 262144)
  *   lazy_filter (0/1), lazy_min_rows — filters fused into the consuming kernel (default >= 1 M rows)
  *   join_ordered, join_chained, join_radix, join_radix_min_rows, join_radix_min_table_bytes, join_radix_part_bytes, probe_batch
  *   join_direct, join_rank, join_coarse (0/1) — the direct / rank-bitmap / LDS coarse-bitmap table layouts (default on)
@@ -509,7 +509,7 @@ typedef struct {
    int32_t avg_pow10;
    /* result column type written to the output table: LDB_T_INT64 (COUNT, integer SUM),
     * LDB_T_DECIMAL128 (out_precision, out_scale), LDB_T_DATE32 / LDB_T_INT32 / LDB_T_CHAR4
-    * (MIN/MAX/ANY of such columns), LDB_T_FLOAT64 */
+    * (MIN/MAX/ANY of such columns), LDB_T_FLOAT64, LDB_T_UTF8 (MIN/MAX of a utf8 column, see below) */
    int32_t out_type;
    int32_t out_precision;
    int32_t out_scale;
@@ -526,7 +526,16 @@ typedef struct {
  * PreAggregationHashtable::merge (:76-158), Hashtable (Hashtable.cpp) and, for n_keys == 0,
  * SimpleState (SimpleState.cpp:8-30).  `preds` are fused into the same pass (the scan is not
  * materialised).  Output table: key columns (input types) then one column per aggregate.
- * Group order is unspecified (as in the reference).  est_groups: optimiser estimate, 0 = unknown. */
+ * Group order is unspecified (as in the reference).  est_groups: optimiser estimate, 0 = unknown.
+ * MIN / MAX over a utf8 column (the select list of every Join Order Benchmark query): fn = LDB_AGG_MIN / LDB_AGG_MAX, arg = the bare
+ * column (one term of one factor: has_col = 1, a = 0, b = 1, no negate / div_pow10 / is_float), out_type = LDB_T_UTF8, n_preds = 0.  The
+ * order is StringRuntime::compareLt / compareGt (src/runtime/StringRuntime.cpp:240-248): unsigned bytes, then length.  NULL arguments
+ * (outer-join padding included) are skipped, a group without a non-NULL argument gives NULL, a key-less aggregate over no rows one NULL
+ * row; the result column is a nullable utf8 column.  n_keys == 0: strings of any length, with or without a dictionary (`preds` are
+ * evaluated by a scan first).  n_keys > 0: the column must carry a dictionary (ldb_gpu_table_dict_encode) — the result shares it;
+ * without one: LDB_ERR_UNSUPPORTED.  Any other expression over a utf8 column and a conditional string aggregate are
+ * LDB_ERR_UNSUPPORTED; a utf8 argument with another out_type, or out_type utf8 with another argument, LDB_ERR_INVALID.  String and
+ * other aggregates mix freely in one call. */
 int32_t ldb_gpu_groupby(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_desc* preds, int32_t n_preds,
                         const ldb_colref* keys, int32_t n_keys, const ldb_agg_spec* aggs, int32_t n_aggs,
                         int64_t est_groups, ldb_table** out);

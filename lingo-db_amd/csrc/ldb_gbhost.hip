@@ -269,6 +269,7 @@ struct GbBuilder {
    ldb_rel* in;
    DGroupBy* h;
    std::vector<ldb_colref> col_refs;
+   bool str_codes = false; // the expression being converted is a string MIN / MAX argument (gb_str_arg): read the column's dictionary codes
    int32_t add_col(ldb_colref ref, int32_t* idx) {
       for (size_t k = 0; k < col_refs.size(); k++)
          if (col_refs[k].side == ref.side && col_refs[k].col == ref.col) {
@@ -277,7 +278,10 @@ struct GbBuilder {
          }
       if (col_refs.size() >= GB_MAX_COLS) LDB_FAIL(LDB_ERR_UNSUPPORTED, "groupby: more than %d distinct aggregate input columns", GB_MAX_COLS);
       DCol dc;
-      LDB_TRY(ldb_make_dcol(in, ref, &dc));
+      if (str_codes) // grouped MIN / MAX over a dictionary-encoded string: the int32 codes stand in (order-preserving, ldb_dict.hip)
+         LDB_TRY(ldb_make_dcol_dict(in, ref, &dc));
+      else
+         LDB_TRY(ldb_make_dcol(in, ref, &dc));
       if (dc.type == LDB_T_UTF8) LDB_FAIL(LDB_ERR_UNSUPPORTED, "groupby: string column in an aggregate expression");
       h->cols[col_refs.size()] = dc;
       *idx = (int32_t) col_refs.size();
@@ -314,7 +318,8 @@ struct GbBuilder {
                *nullable = *nullable || c.validity != nullptr || (sd.rowids && sd.may_null);
                bool colf = c.type.type == LDB_T_FLOAT64 || c.type.type == LDB_T_FLOAT32;
                if (colf && !e->is_float) LDB_FAIL(LDB_ERR_INVALID, "expression: float column in an integer expression (set is_float)");
-               long double cb = c.width >= 8 ? 9.3e18L : (long double) (1ull << (8 * c.width - 1)); // |v| <= 2^(8w-1)
+               const int cw = c.type.type == LDB_T_UTF8 ? 4 : c.width; // (a string column is read as its int32 dictionary codes)
+               long double cb = cw >= 8 ? 9.3e18L : (long double) (1ull << (8 * cw - 1)); // |v| <= 2^(8w-1)
                if (c.type.type == LDB_T_DECIMAL128) {
                   long double pb = 1.0L;
                   for (int k = 0; k < c.type.precision; k++) pb *= 10.0L;
@@ -341,10 +346,138 @@ static bool same_acc(const DAcc& a, const DAcc& b) {
    return memcmp(&a.e, &b.e, sizeof(DExprG)) == 0;
 }
 
+// ---------------------------------------------------------------- MIN / MAX over utf8 columns
+// one selection row per aggregate: the row of the extreme string, LDB_NULL_ROW when every argument is NULL (ldb_strminmax.hip)
+int32_t ldb_str_minmax(ldb_ctx* ctx, const ldb_rel* in, const ldb_colref* cols, const int32_t* is_max, int32_t n, uint32_t** sel_out);
+
+// Does the aggregate read a utf8 column?  The only such shape is MIN / MAX of the bare column (one term, one factor, a = 0, b = 1) with
+// a utf8 result and no predicates of its own; *ref = that column.
+static int32_t gb_str_arg(const ldb_rel* in, const ldb_agg_spec& sp, int32_t a, bool* is_str, ldb_colref* ref) {
+   *is_str = false;
+   if (sp.fn == LDB_AGG_COUNT_STAR) return LDB_OK;
+   bool any = false;
+   for (int t = 0; t < sp.arg.n_terms && t < LDB_MAX_TERMS; t++)
+      for (int f = 0; f < sp.arg.t[t].n_factors && f < LDB_MAX_FACTORS; f++) {
+         const ldb_factor& fa = sp.arg.t[t].f[f];
+         if (!fa.has_col || fa.col.side < 0 || (size_t) fa.col.side >= in->sides.size()) continue; // (a bad reference is reported where it is resolved)
+         const ldb_table* tb = in->sides[(size_t) fa.col.side].table;
+         if (fa.col.col >= 0 && (size_t) fa.col.col < tb->cols.size() && tb->cols[(size_t) fa.col.col].type.type == LDB_T_UTF8) any = true;
+      }
+   if (!any) {
+      if (sp.out_type == LDB_T_UTF8 && sp.fn != LDB_AGG_COUNT) LDB_FAIL(LDB_ERR_INVALID, "groupby: aggregate %d has a utf8 result type but no string argument", a);
+      return LDB_OK;
+   }
+   const ldb_term& tm = sp.arg.t[0];
+   if ((sp.fn != LDB_AGG_MIN && sp.fn != LDB_AGG_MAX) || sp.arg.n_terms != 1 || sp.arg.is_float || tm.n_factors != 1 || tm.negate || tm.div_pow10 || !tm.f[0].has_col || tm.f[0].a != 0 ||
+       tm.f[0].b != 1)
+      LDB_FAIL(LDB_ERR_UNSUPPORTED, "groupby: string column in an aggregate expression (only MIN / MAX of the bare column)");
+   if (sp.out_type != LDB_T_UTF8) LDB_FAIL(LDB_ERR_INVALID, "groupby: aggregate %d is a MIN / MAX over a string column, its result type must be utf8 (got %d)", a, sp.out_type);
+   if (sp.n_preds != 0) LDB_FAIL(LDB_ERR_UNSUPPORTED, "groupby: conditional MIN / MAX over a string column");
+   *is_str = true;
+   *ref = tm.f[0].col;
+   return LDB_OK;
+}
+
+namespace {
+struct GbRelHold {
+   ldb_ctx* ctx;
+   ldb_rel* r = nullptr;
+   ~GbRelHold() {
+      if (r) ldb_gpu_rel_release(ctx, r);
+   }
+};
+struct GbTabHold {
+   ldb_ctx* ctx;
+   ldb_table* t = nullptr;
+   ~GbTabHold() {
+      if (t) ldb_gpu_table_release(ctx, t);
+   }
+};
+} // namespace
+
+// The Join Order Benchmark's aggregate: no keys, MIN / MAX over strings (possibly beside other aggregates).  The filter runs first, the other
+// aggregates go through the key-less path below on the filtered relation, all string aggregates through ldb_str_minmax together; each
+// winning row is a one-row selection whose string the ordinary gather writes (a lazy dictionary column stays codes + dictionary until
+// somebody needs the bytes).  One result row.
+static int32_t gb_keyless_strings(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_desc* preds, int32_t n_preds, const ldb_agg_spec* aggs, int32_t n_aggs, const std::vector<bool>& is_str,
+                                  const std::vector<ldb_colref>& refs, ldb_table** out) {
+   LDB_TRY(ldb_rel_force(ctx, in));
+   GbRelHold filtered{ctx};
+   ldb_rel* cur = in;
+   if (n_preds > 0) {
+      LDB_TRY(ldb_gpu_scan_filter(ctx, in, preds, n_preds, &filtered.r));
+      LDB_TRY(ldb_rel_force(ctx, filtered.r));
+      cur = filtered.r;
+   }
+   if (cur->n_rows >= (int64_t) LDB_NULL_ROW) LDB_FAIL(LDB_ERR_UNSUPPORTED, "groupby: too many rows");
+   std::vector<ldb_agg_spec> rest;
+   std::vector<ldb_colref> scols;
+   std::vector<int32_t> smax;
+   for (int32_t a = 0; a < n_aggs; a++) {
+      if (!is_str[(size_t) a]) {
+         rest.push_back(aggs[a]);
+         continue;
+      }
+      const ldb_colref ref = refs[(size_t) a];
+      if (ref.side < 0 || (size_t) ref.side >= cur->sides.size() || ref.col < 0 || (size_t) ref.col >= cur->sides[(size_t) ref.side].table->cols.size())
+         LDB_FAIL(LDB_ERR_INVALID, "groupby: aggregate %d: column %d:%d out of range", a, ref.side, ref.col);
+      scols.push_back(ref);
+      smax.push_back(aggs[a].fn == LDB_AGG_MAX ? 1 : 0);
+   }
+   GbTabHold part{ctx}, res{ctx};
+   if (!rest.empty()) LDB_TRY(ldb_gpu_groupby(ctx, cur, nullptr, 0, nullptr, 0, rest.data(), (int32_t) rest.size(), 1, &part.t));
+   LdbBufs bufs(ctx);
+   std::vector<uint32_t*> sels(scols.size(), nullptr);
+   for (auto& s : sels) LDB_TRY(bufs.alloc(&s, sizeof(uint32_t)));
+   LDB_TRY(ldb_str_minmax(ctx, cur, scols.data(), smax.data(), (int32_t) scols.size(), sels.data()));
+   res.t = new ldb_table();
+   res.t->ctx = ctx;
+   res.t->name = "groupby";
+   res.t->n_rows = 1;
+   res.t->cols.resize((size_t) n_aggs);
+   size_t at_rest = 0, at_str = 0;
+   for (int32_t a = 0; a < n_aggs; a++) {
+      ldb_column& c = res.t->cols[(size_t) a];
+      if (is_str[(size_t) a]) {
+         GbRelHold one{ctx};
+         bufs.keep(sels[at_str]); // (ldb_rel_select takes the selection over)
+         LDB_TRY(ldb_rel_select(ctx, cur, sels[at_str], 1, &one.r));
+         for (auto& s : one.r->sides) s.may_null = true; // no non-NULL argument: the selection holds LDB_NULL_ROW and the result is NULL
+         LDB_TRY(ldb_gather_columns(ctx, one.r, &scols[at_str], 1, &c));
+         c.type.nullable = 1;
+         at_str++;
+      } else {
+         c = part.t->cols[at_rest]; // the buffers move over with the column
+         part.t->cols[at_rest].owned = false;
+         part.t->cols[at_rest].dict = nullptr;
+         part.t->cols[at_rest].dict_codes = nullptr;
+         at_rest++;
+      }
+      char nm[32];
+      snprintf(nm, sizeof(nm), "agg%d", a);
+      c.name = nm;
+   }
+   *out = res.t;
+   res.t = nullptr;
+   return LDB_OK;
+}
+
 extern "C" int32_t ldb_gpu_groupby(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_desc* preds, int32_t n_preds, const ldb_colref* keys, int32_t n_keys,
                                    const ldb_agg_spec* aggs, int32_t n_aggs, int64_t est_groups, ldb_table** out) {
    if (!ctx || !in || !out) LDB_FAIL(LDB_ERR_INVALID, "groupby: NULL argument");
    if (n_preds < 0 || n_preds > LDB_MAX_PREDS) LDB_FAIL(LDB_ERR_UNSUPPORTED, "groupby: %d predicates (max %d)", n_preds, LDB_MAX_PREDS);
+   // MIN / MAX over utf8 columns: key-less → the string reduction; grouped → the dictionary codes through the integer accumulators
+   std::vector<bool> is_str((size_t) std::max(n_aggs, 0), false);
+   std::vector<ldb_colref> str_ref((size_t) std::max(n_aggs, 0), ldb_colref{0, 0});
+   bool any_str = false;
+   if (n_aggs <= GB_MAX_OUT)
+      for (int32_t a = 0; a < n_aggs; a++) {
+         bool s = false;
+         LDB_TRY(gb_str_arg(in, aggs[a], a, &s, &str_ref[(size_t) a]));
+         is_str[(size_t) a] = s;
+         any_str = any_str || s;
+      }
+   if (any_str && n_keys == 0) return gb_keyless_strings(ctx, in, preds, n_preds, aggs, n_aggs, is_str, str_ref, out);
    if (in->pending.size() + (size_t) n_preds > LDB_MAX_PREDS) LDB_TRY(ldb_rel_force(ctx, in)); // else: a lazy input's conjuncts are fused below
    if (n_keys == 0 && !in->pending.empty()) // key-less ANY needs a representative row that passed the filter: materialise a lazy input
       for (int32_t a = 0; a < n_aggs; a++)
@@ -438,7 +571,17 @@ extern "C" int32_t ldb_gpu_groupby(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_d
          acc.cpred[p] = found;
       }
       bool nullable = false;
+      const bool str = is_str[(size_t) a];
+      if (str) { // grouped: only a dictionary makes a string a fixed-width value (an arg-min accumulator in every layout is the follow-up)
+         const ldb_colref sr = str_ref[(size_t) a];
+         if (sr.col < 0 || (size_t) sr.col >= in->sides[(size_t) sr.side].table->cols.size()) LDB_FAIL(LDB_ERR_INVALID, "groupby: aggregate %d: column %d:%d out of range", a, sr.side, sr.col);
+         const ldb_column& sc = in->sides[(size_t) sr.side].table->cols[(size_t) sr.col];
+         if (!sc.dict_codes || !sc.dict) LDB_FAIL(LDB_ERR_UNSUPPORTED, "groupby: grouped MIN / MAX over a string column without a dictionary");
+         o.wide = 0;
+      }
+      b.str_codes = str;
       if (sp.fn != LDB_AGG_COUNT_STAR) LDB_TRY(b.conv_expr(&sp.arg, &acc.e, &nullable));
+      b.str_codes = false;
       o.e = acc.e;
       // counter of contributing rows: AVG divisor, and NULL-ness of SUM/MIN/MAX results
       auto need_counter = [&](int32_t* idx) -> int32_t {
@@ -504,7 +647,7 @@ extern "C" int32_t ldb_gpu_groupby(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_d
          }
          case LDB_AGG_MIN:
          case LDB_AGG_MAX: {
-            if (sp.wide && !sp.arg.is_float) { // low word, signed high word, lock word (d_sink_minmax128)
+            if (sp.wide && !sp.arg.is_float && !str) { // low word, signed high word, lock word (d_sink_minmax128)
                acc.kind = sp.fn == LDB_AGG_MIN ? ACC_MIN128 : ACC_MAX128;
                LDB_TRY(add_acc(acc, 3, 0, &o.acc));
                const int w0 = h->accs[o.acc].word;
@@ -537,6 +680,7 @@ extern "C" int32_t ldb_gpu_groupby(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_d
       ot.nullable = 1;
       if (o.is_float) ot.type = LDB_T_FLOAT64;
       if (sp.fn == LDB_AGG_COUNT || sp.fn == LDB_AGG_COUNT_STAR) ot.type = LDB_T_INT64;
+      if (str) ot.type = LDB_T_INT32; // the kernels write the winning code; the column becomes codes + the shared dictionary below
       int w = ldb_width_of(ot, 0);
       if (w != 4 && w != 8 && w != 16) LDB_FAIL(LDB_ERR_INVALID, "groupby: aggregate %d output type %d unsupported", a, ot.type);
       o.out_width = w;
@@ -964,6 +1108,19 @@ extern "C" int32_t ldb_gpu_groupby(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_d
       c.values = out_vals[(size_t) a];
       c.value_bytes = (int64_t) n_groups * c.width;
       c.owned = true;
+      if (is_str[(size_t) a]) { // a LAZY utf8 column (ldb_column_is_lazy): the codes the kernels wrote + the argument column's dictionary
+         const ldb_column& sc = in->sides[(size_t) str_ref[(size_t) a].side].table->cols[(size_t) str_ref[(size_t) a].col];
+         c.type = sc.type;
+         c.type.nullable = 1;
+         c.width = sc.width;
+         c.dict_codes = (uint32_t*) c.values;
+         c.values = nullptr;
+         c.value_bytes = -1;
+         c.dict = sc.dict;
+         c.dict->dict_refs++;
+         c.dict_size = sc.dict_size;
+         c.dict_pred_cache = new std::unordered_map<std::string, std::string>();
+      }
       if (bitmaps[(size_t) a]) { // drop the bitmap when nothing is NULL
          const int64_t nulls = (int64_t) ctl[2 + a];
          if (nulls) {

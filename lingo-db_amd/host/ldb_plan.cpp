@@ -666,6 +666,7 @@ struct Interp {
          }
          f.isCol = true;
          f.col = resolve(sides, e.str, "aggregate");
+         if (typeOf(sides, f.col).type == LDB_T_UTF8) throw std::runtime_error("plan: the string column '" + e.str + "' inside an aggregate expression (only min / max of the bare column)");
          f.type = scalarOfCol(typeOf(sides, f.col));
          if (f.type.isFloat()) throw std::runtime_error("plan: aggregate over a float column is not built in the plan language");
          return f;
@@ -675,6 +676,7 @@ struct Interp {
          if (a.kind == J::ARR && a.arr.size() == 2 && a.arr[0].kind == J::NUM && a.arr[1].kind == J::STR) {
             f.constPlus = true;
             f.col = resolve(sides, a.arr[1].str, "aggregate");
+            if (typeOf(sides, f.col).type == LDB_T_UTF8) throw std::runtime_error("plan: the string column '" + a.arr[1].str + "' inside an aggregate expression (only min / max of the bare column)");
             const Scalar ct = scalarOfCol(typeOf(sides, f.col));
             if (ct.isFloat()) throw std::runtime_error("plan: aggregate over a float column is not built in the plan language");
             f.sign = e.obj[0].first == "add" ? 1 : -1;
@@ -965,6 +967,22 @@ struct Interp {
                a.fn = LDB_AGG_COUNT_STAR;
                a.out_type = LDB_T_INT64;
             } else {
+               // min / max over a utf8 column: the bare column name, a utf8 result (bytewise order, StringRuntime::compareLt / compareGt)
+               const J& je = ja.at("expr");
+               __int128 litv;
+               Scalar litt;
+               const bool strArg = je.kind == J::STR && !decimalLiteral(je.str, &litv, &litt) && typeOf(*sides, resolve(*sides, je.str, "aggregate")).type == LDB_T_UTF8;
+               if (strArg) {
+                  if (fn != "min" && fn != "max") throw std::runtime_error("groupby: '" + fn + "' over the string column '" + je.str + "' (only min / max)");
+                  if (a.n_preds) throw std::runtime_error("groupby: conditional " + fn + " over the string column '" + je.str + "' is not supported");
+                  a.fn = fn == "min" ? LDB_AGG_MIN : LDB_AGG_MAX;
+                  a.arg.n_terms = 1;
+                  a.arg.t[0].n_factors = 1;
+                  a.arg.t[0].f[0] = {1, resolve(*sides, je.str, "aggregate"), 0, 1};
+                  a.out_type = LDB_T_UTF8;
+                  aggs.push_back(a);
+                  continue;
+               }
                const Scalar t = aggExpr(*sides, ja.at("expr"), &a.arg);
                if (const J* cnt = ja.get("count")) { // AVG over exchanged partials: SUM(expr) / SUM(count) — the merge of (sum, count) pairs
                   if (fn != "avg") throw std::runtime_error("groupby: 'count' belongs to fn avg");

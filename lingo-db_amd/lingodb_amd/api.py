@@ -144,6 +144,13 @@ def agg(fn, e=None, *, wide=False, out_type=capi.T_INT64, p=0, s=0, preds=(), av
     return a
 
 
+def str_minmax(fn, col):
+    """MIN / MAX over a utf8 column: the bare column as the argument, a utf8 result (bytewise order, a prefix sorts first)."""
+    if fn not in (capi.AGG_MIN, capi.AGG_MAX):
+        raise ValueError("str_minmax: fn must be AGG_MIN or AGG_MAX")
+    return agg(fn, col_expr(col), out_type=capi.T_UTF8)
+
+
 def sort_spec(col, descending=False):
     s = SortSpec()
     s.col = colref(*col)
