@@ -229,6 +229,9 @@ int32_t ldb_gpu_desc_cache_stats(ldb_ctx* ctx, int64_t* hits, int64_t* misses, i
 /* references operators hold on cached descriptors right now (0 between operator calls: every holder gives its reference back on every
  * path, so an unused entry can always be evicted) and the number of references ever given back that nobody held (0: a caller's bug) */
 int32_t ldb_gpu_desc_cache_held(ldb_ctx* ctx, int64_t* held, int64_t* underflows);
+/* device blocks handed out by the context's allocator and not given back yet, and their bytes (size classes) — blocks the descriptor
+ * cache owns are not counted; parked_bytes: freed blocks kept for reuse.  Equal before and after any operator call once its outputs are released */
+int32_t ldb_gpu_mem_stats(ldb_ctx* ctx, int64_t* live_blocks, int64_t* live_bytes, int64_t* parked_bytes);
 
 /* ------------------------------------------------------------------ tables (a1) */
 /* Replaces LingoDBTable::ensureLoaded + TableChunk flattening (LingoDBTable.cpp:27-54,

@@ -546,35 +546,6 @@ __global__ void k_pick_i64(const int64_t* __restrict__ src, PickList pl, int64_t
 // recv_cnt[p] rows from it; the result holds the received rows in peer order.  allgather = every peer
 // gets all rows; alltoall = ldb_gpu_partition's layout.
 namespace {
-struct DevBufs { // device temporaries of one exchange: released on every return path
-   ldb_ctx* ctx;
-   std::vector<void*> ptrs;
-   explicit DevBufs(ldb_ctx* c) : ctx(c) {}
-   ~DevBufs() {
-      for (void* p : ptrs) ldb_dev_free(ctx, p);
-   }
-   template <typename T>
-   int32_t alloc(T** out, size_t bytes) {
-      void* p = nullptr;
-      LDB_TRY(ldb_dev_alloc(ctx, &p, bytes ? bytes : 8));
-      ptrs.push_back(p);
-      *out = (T*) p;
-      return LDB_OK;
-   }
-};
-struct TableGuard { // the partially built result table
-   ldb_ctx* ctx;
-   ldb_table* t = nullptr;
-   explicit TableGuard(ldb_ctx* c) : ctx(c) {}
-   ~TableGuard() {
-      if (t) ldb_gpu_table_release(ctx, t);
-   }
-   ldb_table* release() {
-      ldb_table* r = t;
-      t = nullptr;
-      return r;
-   }
-};
 struct GroupGuard { // never leave a transfer group open on an error return
    Transport* t;
    bool open = false;
@@ -607,23 +578,18 @@ static int32_t alloc_like(ldb_ctx* ctx, const ldb_table* t, const char* name, in
       types[(size_t) k] = t->cols[(size_t) k].type;
       names[(size_t) k] = t->cols[(size_t) k].name.c_str();
    }
-   ldb_table* res = nullptr;
-   LDB_TRY(ldb_gpu_table_alloc(ctx, name, nc, types.data(), names.data(), n_rows, data_bytes.data(), 0, &res));
+   LdbTableHold res(ctx);
+   LDB_TRY(ldb_gpu_table_alloc(ctx, name, nc, types.data(), names.data(), n_rows, data_bytes.data(), 0, &res.t));
    for (int k = 0; k < nc; k++) {
       const ldb_column& src = t->cols[(size_t) k];
       ldb_column& dst = res->cols[(size_t) k];
       if (src.type.type == LDB_T_UTF8 || dst.width == src.width) continue;
-      ldb_dev_free(ctx, dst.values);
-      dst.values = nullptr;
+      LdbBufs::drop(ctx, &dst.values);
       dst.width = src.width;
       dst.value_bytes = n_rows * (int64_t) src.width;
-      const int32_t st = ldb_dev_alloc(ctx, &dst.values, (size_t) (dst.value_bytes ? dst.value_bytes : 8));
-      if (st != LDB_OK) {
-         ldb_gpu_table_release(ctx, res);
-         return st;
-      }
+      LDB_TRY(LdbBufs::alloc_into(ctx, &dst.values, (size_t) dst.value_bytes));
    }
-   *out = res;
+   *out = res.release();
    return LDB_OK;
 }
 
@@ -634,7 +600,7 @@ static int32_t exchange(ldb_ctx* ctx, ldb_comm* c, const ldb_table* t, const std
    for (auto& col : t->cols) // the exchange ships string bytes: dictionary-coded (lazy) columns are written out first
       if (ldb_column_is_lazy(col)) LDB_TRY(ldb_column_strings(ctx, col, t->n_rows));
    Transport* tr = c->t.get();
-   DevBufs bufs(ctx);
+   LdbBufs bufs(ctx);
    std::vector<int> ucols; // utf8 columns
    for (int k = 0; k < nc; k++)
       if (t->cols[(size_t) k].type.type == LDB_T_UTF8) ucols.push_back(k);
@@ -721,7 +687,7 @@ static int32_t exchange(ldb_ctx* ctx, ldb_comm* c, const ldb_table* t, const std
       for (int p = 0; p < world; p++) any_valid[(size_t) k] = any_valid[(size_t) k] || rmeta[(size_t) p * mw + 1 + nu + 3 * k] != 0;
    for (int u = 0; u < nu; u++)
       for (int p = 0; p < world; p++) data_bytes[(size_t) ucols[(size_t) u]] += rmeta[(size_t) p * mw + 1 + u];
-   TableGuard res(ctx);
+   LdbTableHold res(ctx);
    LDB_TRY(alloc_like(ctx, t, name ? name : "exchanged", n_all, data_bytes, &res.t));
    const int64_t n_mine = t->n_rows;
    const int grid_in = ldb_grid_for(ctx, n_mine, 256, 8), grid_out = ldb_grid_for(ctx, n_all, 256, 8);
@@ -784,7 +750,7 @@ static int32_t exchange(ldb_ctx* ctx, ldb_comm* c, const ldb_table* t, const std
       LDB_HIP(hipMemsetAsync(d_nulls, 0, 8 * vcols.size(), ctx->stream));
       for (size_t v = 0; v < vcols.size(); v++) {
          ldb_column& dst = res.t->cols[(size_t) vcols[v]];
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &dst.validity, (size_t) ((n_all + 7) / 8 + 1)));
+         LDB_TRY(LdbBufs::alloc_into(ctx, &dst.validity, (size_t) ((n_all + 7) / 8 + 1)));
          if (n_all) {
             hipLaunchKernelGGL(k_bytes_to_bits, dim3(grid_out), dim3(256), 0, ctx->stream, (const uint8_t*) vb_out[(size_t) vcols[v]], dst.validity, (uint64_t) n_all);
             hipLaunchKernelGGL(k_count_zero_bytes, dim3(grid_out), dim3(256), 0, ctx->stream, (const uint8_t*) vb_out[(size_t) vcols[v]], (uint64_t) n_all, d_nulls + v);
@@ -824,7 +790,7 @@ extern "C" int32_t ldb_gpu_alltoall(ldb_ctx* ctx, ldb_comm* c, const ldb_table* 
 extern "C" int32_t ldb_gpu_shuffle(ldb_ctx* ctx, ldb_comm* c, ldb_rel* in, const ldb_colref* keys, int32_t n_keys, const ldb_colref* cols, int32_t n_cols, const char* name,
                                    ldb_table** out) {
    if (!ctx || !c || !in || !out) LDB_FAIL(LDB_ERR_INVALID, "shuffle: NULL argument");
-   TableGuard packed(ctx);
+   LdbTableHold packed(ctx);
    std::vector<int64_t> counts((size_t) c->world, 0);
    LDB_TRY(ldb_gpu_partition(ctx, in, keys, n_keys, c->world, cols, n_cols, &packed.t, counts.data()));
    return ldb_gpu_alltoall(ctx, c, packed.t, counts.data(), name, out);
@@ -841,16 +807,11 @@ extern "C" int32_t ldb_gpu_comm_agree(ldb_ctx* ctx, ldb_comm* c, int32_t mine, i
    std::vector<int64_t> h((size_t) world + 1, 0);
    h[0] = mine;
    int64_t *send = h.data(), *recv = h.data() + 1;
-   void* dev = nullptr;
+   LdbBufs tmp(ctx);
    if (ctx) { // a device communicator moves device memory: [mine | one word per peer]
-      LDB_TRY(ldb_dev_alloc(ctx, &dev, 8 * ((size_t) world + 1)));
-      send = (int64_t*) dev;
+      LDB_TRY(tmp.alloc(&send, 8 * ((size_t) world + 1)));
       recv = send + 1;
-      const int32_t st = ldb_h2d_small(ctx, send, h.data(), 8);
-      if (st != LDB_OK) {
-         ldb_dev_free(ctx, dev);
-         return st;
-      }
+      LDB_TRY(ldb_h2d_small(ctx, send, h.data(), 8));
    }
    int32_t st = LDB_OK;
    {
@@ -872,7 +833,6 @@ extern "C" int32_t ldb_gpu_comm_agree(ldb_ctx* ctx, ldb_comm* c, int32_t mine, i
          memcpy(h.data() + 1, ctx->h_scratch, 8 * (size_t) std::min(world, 63));
       }
    }
-   if (ctx) ldb_dev_free(ctx, dev);
    if (st != LDB_OK) return st;
    int64_t m = mine;
    for (int p = 0; p < world; p++) m = std::min(m, h[(size_t) p + 1]);

@@ -535,6 +535,19 @@ extern "C" int32_t ldb_gpu_desc_cache_held(ldb_ctx* ctx, int64_t* held, int64_t*
    if (underflows) *underflows = ctx->desc_underflows;
    return LDB_OK;
 }
+extern "C" int32_t ldb_gpu_mem_stats(ldb_ctx* ctx, int64_t* live_blocks, int64_t* live_bytes, int64_t* parked_bytes) {
+   if (!ctx) LDB_FAIL(LDB_ERR_INVALID, "mem_stats: NULL ctx");
+   int64_t blocks = 0, bytes = 0;
+   for (auto& b : ctx->live)
+      if (!ctx->desc_blocks.count(b.first)) {
+         blocks++;
+         bytes += (int64_t) b.second;
+      }
+   if (live_blocks) *live_blocks = blocks;
+   if (live_bytes) *live_bytes = bytes;
+   if (parked_bytes) *parked_bytes = (int64_t) ctx->cache_bytes;
+   return LDB_OK;
+}
 extern "C" int32_t ldb_gpu_desc_cache_stats(ldb_ctx* ctx, int64_t* hits, int64_t* misses, int64_t* bytes) {
    if (!ctx) LDB_FAIL(LDB_ERR_INVALID, "desc_cache_stats: NULL ctx");
    if (hits) *hits = ctx->desc_hits;
@@ -795,7 +808,7 @@ extern "C" int32_t ldb_gpu_table_register(ldb_ctx* ctx, const char* name, struct
                                           int64_t n_batches, int32_t narrow, ldb_table** out) {
    if (!ctx || !schema || !out) LDB_FAIL(LDB_ERR_INVALID, "table_register: NULL argument");
    if (strcmp(schema->format, "+s")) LDB_FAIL(LDB_ERR_INVALID, "table_register: schema must be a struct (+s), got %s", schema->format);
-   auto t = std::make_unique<ldb_table>();
+   LdbTableHold t(ctx, new ldb_table());
    t->ctx = ctx;
    t->name = name ? name : "";
    int64_t rows = 0;
@@ -847,7 +860,7 @@ extern "C" int32_t ldb_gpu_table_register(ldb_ctx* ctx, const char* name, struct
                else col.null_count++;
             }
          }
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &col.validity, bm.size()));
+         LDB_TRY(LdbBufs::alloc_into(ctx, &col.validity, bm.size()));
          LDB_HIP(hipMemcpyAsync(col.validity, bm.data(), bm.size(), hipMemcpyHostToDevice, ctx->stream));
          LDB_HIP(hipStreamSynchronize(ctx->stream));
       }
@@ -874,8 +887,8 @@ extern "C" int32_t ldb_gpu_table_register(ldb_ctx* ctx, const char* name, struct
             }
          }
          col.value_bytes = bytes;
-         LDB_TRY(ldb_dev_alloc(ctx, &col.values, (size_t) bytes));
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &col.offsets, sizeof(int64_t) * ((size_t) rows + 1)));
+         LDB_TRY(LdbBufs::alloc_into(ctx, &col.values, (size_t) bytes));
+         LDB_TRY(LdbBufs::alloc_into(ctx, &col.offsets, sizeof(int64_t) * ((size_t) rows + 1)));
          LDB_HIP(hipMemcpyAsync(col.offsets, offs.data(), sizeof(int64_t) * ((size_t) rows + 1), hipMemcpyHostToDevice, ctx->stream));
          int64_t dpos = 0;
          for (int64_t b = 0; b < n_batches; b++) {
@@ -922,7 +935,7 @@ extern "C" int32_t ldb_gpu_table_register(ldb_ctx* ctx, const char* name, struct
             if (col.type.type == LDB_T_CHAR4 && (col.width > 1 || lo < 0)) col.width = 4; // (a byte >= 0x80 or a second character: the four raw bytes stay)
          }
          col.value_bytes = rows * col.width;
-         LDB_TRY(ldb_dev_alloc(ctx, &col.values, (size_t) col.value_bytes));
+         LDB_TRY(LdbBufs::alloc_into(ctx, &col.values, (size_t) col.value_bytes));
          int64_t pos = 0;
          std::vector<int64_t> tmp;
          for (int64_t b = 0; b < n_batches; b++) {
@@ -945,7 +958,7 @@ extern "C" int32_t ldb_gpu_table_register(ldb_ctx* ctx, const char* name, struct
          LDB_HIP(hipStreamSynchronize(ctx->stream));
       }
    }
-   LDB_TRY(ldb_table_dict_encode_all(ctx, t.get())); // low-cardinality utf8 columns get an order-preserving dictionary
+   LDB_TRY(ldb_table_dict_encode_all(ctx, t.t)); // low-cardinality utf8 columns get an order-preserving dictionary
    *out = t.release();
    return LDB_OK;
 }
@@ -954,7 +967,7 @@ extern "C" int32_t ldb_gpu_table_alloc(ldb_ctx* ctx, const char* name, int32_t n
                                        int64_t n_rows, const int64_t* data_bytes, int32_t narrow, ldb_table** out) {
    if (!ctx || !out || n_cols < 0) LDB_FAIL(LDB_ERR_INVALID, "table_alloc: bad argument");
    if (n_rows >= (int64_t) LDB_NULL_ROW) LDB_FAIL(LDB_ERR_UNSUPPORTED, "table_alloc: %ld rows exceed uint32 row ids", (long) n_rows);
-   auto t = std::make_unique<ldb_table>();
+   LdbTableHold t(ctx, new ldb_table());
    t->ctx = ctx;
    t->name = name ? name : "";
    t->n_rows = n_rows;
@@ -966,11 +979,11 @@ extern "C" int32_t ldb_gpu_table_alloc(ldb_ctx* ctx, const char* name, int32_t n
       col.width = ldb_width_of(col.type, narrow);
       if (col.type.type == LDB_T_UTF8) {
          col.value_bytes = data_bytes ? data_bytes[c] : 0;
-         LDB_TRY(ldb_dev_alloc(ctx, &col.values, (size_t) col.value_bytes));
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &col.offsets, sizeof(int64_t) * ((size_t) n_rows + 1)));
+         LDB_TRY(LdbBufs::alloc_into(ctx, &col.values, (size_t) col.value_bytes));
+         LDB_TRY(LdbBufs::alloc_into(ctx, &col.offsets, sizeof(int64_t) * ((size_t) n_rows + 1)));
       } else {
          col.value_bytes = n_rows * col.width;
-         LDB_TRY(ldb_dev_alloc(ctx, &col.values, (size_t) col.value_bytes));
+         LDB_TRY(LdbBufs::alloc_into(ctx, &col.values, (size_t) col.value_bytes));
       }
    }
    *out = t.release();
@@ -1838,6 +1851,7 @@ int32_t ldb_gather_columns(ldb_ctx* ctx, const ldb_rel* r, const ldb_colref* ref
       int64_t* lens = nullptr;
    };
    std::vector<Pending> pend((size_t) n_cols);
+   LdbBufs tmp(ctx); // the string lengths; the outputs belong to the caller's columns
    int n_slots = 0;
    const bool lazy_on = ldb_option("lazy_strings", 1) != 0;
    const uint64_t lazy_min = (uint64_t) ldb_option("lazy_strings_min_rows", 4096);
@@ -1865,13 +1879,13 @@ int32_t ldb_gather_columns(ldb_ctx* ctx, const ldb_rel* r, const ldb_colref* ref
       out->width = src.width;
       out->owned = true;
       if (p.slot_nulls >= 0) {
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &out->validity, (size_t) ((n + 7) / 8 + 8)));
+         LDB_TRY(LdbBufs::alloc_into(ctx, &out->validity, (size_t) ((n + 7) / 8 + 8)));
          if (n) hipLaunchKernelGGL(k_gather_validity, dim3(grid), dim3(256), 0, ctx->stream, src.validity, p.rowids, (uint64_t*) out->validity, n, d_words + p.slot_nulls);
       }
       const bool src_lazy = ldb_column_is_lazy(src);
       if (src.type.type == LDB_T_UTF8 && src.dict_codes && src.dict && (n >= 64 || src_lazy)) {
          // the gathered column inherits the source's dictionary: codes gathered alongside, the dictionary table shared
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &out->dict_codes, 4 * (size_t) (n ? n : 1)));
+         LDB_TRY(LdbBufs::alloc_into(ctx, &out->dict_codes, 4 * (size_t) (n ? n : 1)));
          if (n) hipLaunchKernelGGL(k_gather_fixed<uint32_t>, dim3(grid), dim3(256), 0, ctx->stream, (const uint32_t*) src.dict_codes, p.rowids, out->dict_codes, n);
          out->dict = src.dict;
          out->dict->dict_refs++;
@@ -1884,8 +1898,8 @@ int32_t ldb_gather_columns(ldb_ctx* ctx, const ldb_rel* r, const ldb_colref* ref
          p.slot_bytes = -1;
          lazy_small.push_back(src_lazy && n < 64 ? out : nullptr);
       } else if (src.type.type == LDB_T_UTF8) {
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &p.lens, sizeof(int64_t) * (size_t) (n + 1)));
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &out->offsets, sizeof(int64_t) * (size_t) (n + 1)));
+         LDB_TRY(tmp.alloc(&p.lens, sizeof(int64_t) * (size_t) (n + 1)));
+         LDB_TRY(LdbBufs::alloc_into(ctx, &out->offsets, sizeof(int64_t) * (size_t) (n + 1)));
          hipLaunchKernelGGL(k_str_lens, dim3(grid), dim3(256), 0, ctx->stream, src.offsets, p.rowids, p.lens, n);
          LDB_TRY(ldb_exclusive_scan_i64(ctx, p.lens, out->offsets, (int64_t) n, (int64_t*) (d_words + p.slot_bytes)));
       } else {
@@ -1898,7 +1912,7 @@ int32_t ldb_gather_columns(ldb_ctx* ctx, const ldb_rel* r, const ldb_colref* ref
             out->vmin = src.vmin;
             out->vmax = src.vmax;
          }
-         LDB_TRY(ldb_dev_alloc(ctx, &out->values, (size_t) out->value_bytes));
+         LDB_TRY(LdbBufs::alloc_into(ctx, &out->values, (size_t) out->value_bytes));
          switch (src.width) {
             case 1: hipLaunchKernelGGL(k_gather_fixed<uint8_t>, dim3(grid), dim3(256), 0, ctx->stream, (const uint8_t*) src.values, p.rowids, (uint8_t*) out->values, n); break;
             case 2: hipLaunchKernelGGL(k_gather_fixed<uint16_t>, dim3(grid), dim3(256), 0, ctx->stream, (const uint16_t*) src.values, p.rowids, (uint16_t*) out->values, n); break;
@@ -1923,16 +1937,15 @@ int32_t ldb_gather_columns(ldb_ctx* ctx, const ldb_rel* r, const ldb_colref* ref
       if (p.slot_nulls >= 0) {
          out->null_count = (int64_t) words[(size_t) p.slot_nulls];
          if (out->null_count == 0) {
-            ldb_dev_free(ctx, out->validity);
-            out->validity = nullptr;
+            LdbBufs::drop(ctx, &out->validity);
          }
       }
       if (p.slot_bytes >= 0) {
          const ldb_column& src = r->sides[(size_t) refs[c].side].table->cols[(size_t) refs[c].col];
          const uint64_t total = words[(size_t) p.slot_bytes];
-         ldb_dev_free(ctx, p.lens);
+         tmp.free(p.lens);
          out->value_bytes = (int64_t) total;
-         LDB_TRY(ldb_dev_alloc(ctx, &out->values, (size_t) total));
+         LDB_TRY(LdbBufs::alloc_into(ctx, &out->values, (size_t) total));
          hipLaunchKernelGGL(k_str_copy, dim3(grid), dim3(256), 0, ctx->stream, (const uint8_t*) src.values, src.offsets, p.rowids, out->offsets, (uint8_t*) out->values, n,
                             (int64_t) total);
       }
@@ -1979,16 +1992,12 @@ extern "C" int32_t ldb_gpu_materialize(ldb_ctx* ctx, ldb_rel* r, const ldb_colre
    for (int32_t c = 0; c < n_cols; c++)
       if (cols[c].side < 0 || (size_t) cols[c].side >= r->sides.size() || cols[c].col < 0 || (size_t) cols[c].col >= r->sides[(size_t) cols[c].side].table->cols.size())
          LDB_FAIL(LDB_ERR_INVALID, "materialize: column %d:%d out of range", cols[c].side, cols[c].col);
-   auto t = std::make_unique<ldb_table>();
+   LdbTableHold t(ctx, new ldb_table());
    t->ctx = ctx;
    t->name = "materialized";
    t->n_rows = r->n_rows;
    t->cols.resize((size_t) n_cols);
-   int32_t s = ldb_gather_columns(ctx, r, cols, n_cols, t->cols.data());
-   if (s != LDB_OK) {
-      ldb_gpu_table_release(ctx, t.release());
-      return s;
-   }
+   LDB_TRY(ldb_gather_columns(ctx, r, cols, n_cols, t->cols.data()));
    *out = t.release();
    return LDB_OK;
 }
@@ -2131,16 +2140,15 @@ static int32_t scan_impl(ldb_ctx* ctx, const T* d_in, TO* d_out, int64_t n, TT* 
       if (hipGetLastError() != hipSuccess) return ldb_chain_failed(ctx);
       return LDB_OK;
    }
+   LdbBufs tmp(ctx);
    TO* sums = nullptr;
-   if (nb > 1) LDB_TRY(ldb_dev_alloc(ctx, (void**) &sums, sizeof(TO) * (size_t) (nb + 1)));
+   if (nb > 1) LDB_TRY(tmp.alloc(&sums, sizeof(TO) * (size_t) (nb + 1)));
    hipLaunchKernelGGL((k_scan_block<T, TO, TT>), dim3((unsigned) nb), dim3(256), 0, ctx->stream, d_in, d_out, sums, (uint64_t) n, d_total);
    if (nb > 1) {
       TO* sums_scanned;
-      LDB_TRY(ldb_dev_alloc(ctx, (void**) &sums_scanned, sizeof(TO) * (size_t) (nb + 1)));
+      LDB_TRY(tmp.alloc(&sums_scanned, sizeof(TO) * (size_t) (nb + 1)));
       LDB_TRY((scan_impl<TO, TO, TT, VBITS>(ctx, sums, sums_scanned, nb, d_total)));
       hipLaunchKernelGGL((k_scan_add<TO>), dim3((unsigned) nb), dim3(256), 0, ctx->stream, d_out, sums_scanned, (uint64_t) n);
-      ldb_dev_free(ctx, sums_scanned);
-      ldb_dev_free(ctx, sums);
    }
    LDB_HIP(hipGetLastError());
    return LDB_OK;

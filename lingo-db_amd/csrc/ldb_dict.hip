@@ -42,22 +42,6 @@ void ldb_column_dict_release(ldb_ctx* ctx, ldb_column& c) {
 }
 
 namespace {
-struct Rel {
-   ldb_ctx* ctx;
-   ldb_rel* r = nullptr;
-   explicit Rel(ldb_ctx* c) : ctx(c) {}
-   ~Rel() {
-      if (r) ldb_gpu_rel_release(ctx, r);
-   }
-};
-struct Tab {
-   ldb_ctx* ctx;
-   ldb_table* t = nullptr;
-   explicit Tab(ldb_ctx* c) : ctx(c) {}
-   ~Tab() {
-      if (t) ldb_gpu_table_release(ctx, t);
-   }
-};
 struct Ht {
    ldb_ctx* ctx;
    ldb_hashtable* h = nullptr;
@@ -86,7 +70,7 @@ std::unique_ptr<ldb_table> view_of(const ldb_table* t, int32_t col, int64_t rows
 }
 // distinct non-NULL values of column 0 of `v` → *out (one utf8 column + the count); LDB_OK with *n_distinct > limit when there are too many
 int32_t distinct_of(ldb_ctx* ctx, const ldb_table* v, int64_t limit, ldb_table** out, int64_t* n_distinct) {
-   Rel r(ctx);
+   LdbRelHold r(ctx);
    LDB_TRY(ldb_gpu_rel_from_table(ctx, v, &r.r));
    ldb_filter_desc nn;
    memset(&nn, 0, sizeof(nn));
@@ -112,19 +96,19 @@ int32_t ldb_table_dict_encode(ldb_ctx* ctx, ldb_table* t, int32_t col, int32_t m
    const int64_t sample = std::min<int64_t>(t->n_rows, 1 << 16);
    {
       auto v = view_of(t, col, sample);
-      Tab d(ctx);
+      LdbTableHold d(ctx);
       int64_t nd = 0;
       LDB_TRY(distinct_of(ctx, v.get(), max_distinct, &d.t, &nd));
       if (nd > max_distinct || (sample < t->n_rows && nd * 2 > max_distinct && nd * 8 > sample)) return LDB_OK;
    }
    // 2. the distinct values of the whole column, in string order
    auto v = view_of(t, col, t->n_rows);
-   Tab distinct(ctx), dict(ctx);
+   LdbTableHold distinct(ctx), dict(ctx);
    int64_t nd = 0;
    LDB_TRY(distinct_of(ctx, v.get(), max_distinct, &distinct.t, &nd));
    if (nd > max_distinct || nd == 0) return LDB_OK;
    {
-      Rel dr(ctx), sorted(ctx);
+      LdbRelHold dr(ctx), sorted(ctx);
       LDB_TRY(ldb_gpu_rel_from_table(ctx, distinct.t, &dr.r));
       const ldb_sort_spec by = {{0, 0}, 0, 0};
       LDB_TRY(ldb_gpu_sort(ctx, dr.r, &by, 1, &sorted.r));
@@ -132,7 +116,7 @@ int32_t ldb_table_dict_encode(ldb_ctx* ctx, ldb_table* t, int32_t col, int32_t m
       LDB_TRY(ldb_gpu_materialize(ctx, sorted.r, &k, 1, &dict.t));
    }
    // 3. every row's code = the dictionary row its string matches (SINGLE join: one output row per probe row, in order)
-   Rel dictrel(ctx), rows(ctx), joined(ctx);
+   LdbRelHold dictrel(ctx), rows(ctx), joined(ctx);
    Ht ht(ctx);
    LDB_TRY(ldb_gpu_rel_from_table(ctx, dict.t, &dictrel.r));
    LDB_TRY(ldb_gpu_rel_from_table(ctx, v.get(), &rows.r));
@@ -140,13 +124,14 @@ int32_t ldb_table_dict_encode(ldb_ctx* ctx, ldb_table* t, int32_t col, int32_t m
    LDB_TRY(ldb_gpu_join_build(ctx, dictrel.r, &k, 1, 1, &ht.h));
    LDB_TRY(ldb_gpu_join_probe(ctx, ht.h, rows.r, &k, 1, LDB_JOIN_SINGLE, &joined.r, nullptr));
    if (joined.r->n_rows != t->n_rows || joined.r->sides.size() != 2 || !joined.r->sides[1].rowids) LDB_FAIL(LDB_ERR_INVALID, "dict_encode: unexpected join shape");
+   LdbBufs own(ctx);
    uint32_t* codes = nullptr;
-   LDB_TRY(ldb_dev_alloc(ctx, (void**) &codes, 4 * (size_t) t->n_rows));
+   LDB_TRY(own.alloc(&codes, 4 * (size_t) t->n_rows));
    LDB_HIP(hipMemcpyAsync(codes, joined.r->sides[1].rowids, 4 * (size_t) t->n_rows, hipMemcpyDeviceToDevice, ctx->stream));
    LDB_HIP(hipStreamSynchronize(ctx->stream)); // (the views and relations above die with this scope)
+   own.keep(codes);
    c.dict_codes = codes;
-   c.dict = dict.t;
-   dict.t = nullptr;
+   c.dict = dict.release();
    c.dict_size = (int32_t) nd;
    c.dict_pred_cache = new std::unordered_map<std::string, std::string>();
    return LDB_OK;
@@ -228,7 +213,7 @@ int32_t ldb_dict_rewrite_pred(const ldb_rel* r, const ldb_filter_desc* p, DPred*
       // the same predicate over the dictionary's rows: accepted dictionary rows = accepted codes
       ldb_filter_desc q = *p;
       q.col = {0, 0};
-      Rel dr(ctx), hit(ctx);
+      LdbRelHold dr(ctx), hit(ctx);
       LDB_TRY(ldb_gpu_rel_from_table(ctx, c.dict, &dr.r));
       LDB_TRY(ldb_gpu_scan_filter(ctx, dr.r, &q, 1, &hit.r));
       LDB_TRY(ldb_rel_force(ctx, hit.r));

@@ -91,8 +91,8 @@ bool ldb_fexpr_jit_check(std::string* log) { // cast(a * b + c as double) < 0.5 
 
 static int32_t map_fexpr_launch(ldb_ctx* ctx, const DFProg* hp, int64_t n, ldb_table* res) {
    // one 64-bit word per 64 rows, written whole by the wave that holds those rows
-   uint64_t* bm;
-   LDB_TRY(ldb_dev_alloc(ctx, (void**) &bm, (size_t) ((n + 63) / 64 + 1) * 8));
+   LDB_TRY(LdbBufs::alloc_into(ctx, &res->cols[0].validity, (size_t) ((n + 63) / 64 + 1) * 8));
+   uint64_t* bm = (uint64_t*) res->cols[0].validity;
    if (n) {
       const int grid = ldb_grid_for(ctx, (n + FX_ROWS - 1) / FX_ROWS, 256, 8);
       LdbDesc<DFProg> d_desc(ctx);
@@ -119,7 +119,6 @@ static int32_t map_fexpr_launch(ldb_ctx* ctx, const DFProg* hp, int64_t n, ldb_t
       }
       d_desc.release();
    }
-   res->cols[0].validity = (uint8_t*) bm;
    res->cols[0].null_count = -1; // unknown (Arrow convention)
    res->cols[0].type.nullable = 1;
    LDB_HIP(hipGetLastError());
@@ -284,14 +283,13 @@ extern "C" int32_t ldb_gpu_map_expr(ldb_ctx* ctx, ldb_rel* in, const ldb_xinstr*
    if (xt_is_float(ty[0]) ? ty[0] != out_cls : xt_is_float(out_cls))
       LDB_FAIL(LDB_ERR_INVALID, "map_expr: instruction %d: the program's result is %s, out_type %d is not of that class", n_instr - 1, xt_name(ty[0]), out_type.type);
    const char* nm = name ? name : "expr";
-   ldb_table* res;
-   LDB_TRY(ldb_gpu_table_alloc(ctx, "mapped", 1, &out_type, &nm, in->n_rows, nullptr, 0, &res));
+   LdbTableHold res(ctx);
+   LDB_TRY(ldb_gpu_table_alloc(ctx, "mapped", 1, &out_type, &nm, in->n_rows, nullptr, 0, &res.t));
    const int64_t n = in->n_rows;
    if (has_float) { // typed slots: the float kernel
       fp->out_width = res->cols[0].width;
-      const int32_t st = map_fexpr_launch(ctx, fp.get(), n, res);
-      if (st != LDB_OK) return st;
-      *out = res;
+      LDB_TRY(map_fexpr_launch(ctx, fp.get(), n, res.t));
+      *out = res.release();
       return LDB_OK;
    }
    // integer program: the 128-bit integer interpreter, as it always was
@@ -307,9 +305,11 @@ extern "C" int32_t ldb_gpu_map_expr(ldb_ctx* ctx, ldb_rel* in, const ldb_xinstr*
       hp->ins[k].hi = x.hi;
    }
    hp->out_width = res->cols[0].width;
-   uint8_t *vb, *bm;
-   LDB_TRY(ldb_dev_alloc(ctx, (void**) &vb, (size_t) (n ? n : 1)));
-   LDB_TRY(ldb_dev_alloc(ctx, (void**) &bm, (size_t) ((n + 7) / 8 + 1)));
+   LdbBufs tmp(ctx);
+   uint8_t* vb;
+   LDB_TRY(tmp.alloc(&vb, (size_t) (n ? n : 1)));
+   LDB_TRY(LdbBufs::alloc_into(ctx, &res->cols[0].validity, (size_t) ((n + 7) / 8 + 1)));
+   uint8_t* bm = res->cols[0].validity;
    const int grid = ldb_grid_for(ctx, n, 256, 8);
    if (n) {
       LdbDesc<DXProg> d_desc(ctx);
@@ -337,12 +337,10 @@ extern "C" int32_t ldb_gpu_map_expr(ldb_ctx* ctx, ldb_rel* in, const ldb_xinstr*
       hipLaunchKernelGGL(k_pack_bytes_to_bits_x, dim3(grid), dim3(256), 0, ctx->stream, (const uint8_t*) vb, bm, (uint64_t) n);
       d_desc.release();
    }
-   res->cols[0].validity = bm;
    res->cols[0].null_count = -1; // unknown (Arrow convention)
    res->cols[0].type.nullable = 1;
-   ldb_dev_free(ctx, vb);
    LDB_HIP(hipGetLastError());
-   *out = res;
+   *out = res.release();
    return LDB_OK;
 }
 
@@ -405,35 +403,33 @@ extern "C" int32_t ldb_gpu_map_substr(ldb_ctx* ctx, ldb_rel* in, ldb_colref col,
    const int64_t n = in->n_rows;
    const bool nullable = dc.validity || dc.rowids;
    const int grid = ldb_grid_for(ctx, n, 256, 8);
+   LdbBufs tmp(ctx);
    int64_t* lens;
    uint8_t* vb = nullptr;
-   LDB_TRY(ldb_dev_alloc(ctx, (void**) &lens, 8 * (size_t) (n + 1)));
-   if (nullable) LDB_TRY(ldb_dev_alloc(ctx, (void**) &vb, (size_t) (n ? n : 1)));
+   LDB_TRY(tmp.alloc(&lens, 8 * (size_t) (n + 1)));
+   if (nullable) LDB_TRY(tmp.alloc(&vb, (size_t) (n ? n : 1)));
    if (n) hipLaunchKernelGGL(k_substr_lens, dim3(grid), dim3(256), 0, ctx->stream, dc, from, for_len, (uint64_t) n, lens, vb);
    int64_t* offs;
-   LDB_TRY(ldb_dev_alloc(ctx, (void**) &offs, 8 * (size_t) (n + 1)));
+   LDB_TRY(tmp.alloc(&offs, 8 * (size_t) (n + 1)));
    LDB_TRY(ldb_exclusive_scan_i64(ctx, lens, offs, n, offs + n));
    uint64_t total = 0;
    LDB_TRY(ldb_read_u64(ctx, offs + n, &total));
-   ldb_dev_free(ctx, lens);
+   tmp.free(lens);
    ldb_coltype t = {LDB_T_UTF8, 0, 0, nullable ? 1 : 0};
    const char* nm = name ? name : "substr";
    const int64_t cap = (int64_t) total;
-   ldb_table* res;
-   LDB_TRY(ldb_gpu_table_alloc(ctx, "mapped", 1, &t, &nm, n, &cap, 0, &res));
+   LdbTableHold res(ctx);
+   LDB_TRY(ldb_gpu_table_alloc(ctx, "mapped", 1, &t, &nm, n, &cap, 0, &res.t));
    LDB_HIP(hipMemcpyAsync(res->cols[0].offsets, offs, 8 * (size_t) (n + 1), hipMemcpyDeviceToDevice, ctx->stream));
    res->cols[0].value_bytes = cap;
    if (n) hipLaunchKernelGGL(k_substr_fill, dim3(grid), dim3(256), 0, ctx->stream, dc, from, for_len, (uint64_t) n, (const int64_t*) offs, (uint8_t*) res->cols[0].values);
-   ldb_dev_free(ctx, offs);
+   tmp.free(offs);
    if (nullable) {
-      uint8_t* bm;
-      LDB_TRY(ldb_dev_alloc(ctx, (void**) &bm, (size_t) ((n + 7) / 8 + 1)));
-      if (n) hipLaunchKernelGGL(k_pack_bytes_to_bits_x, dim3(grid), dim3(256), 0, ctx->stream, (const uint8_t*) vb, bm, (uint64_t) n);
-      res->cols[0].validity = bm;
+      LDB_TRY(LdbBufs::alloc_into(ctx, &res->cols[0].validity, (size_t) ((n + 7) / 8 + 1)));
+      if (n) hipLaunchKernelGGL(k_pack_bytes_to_bits_x, dim3(grid), dim3(256), 0, ctx->stream, (const uint8_t*) vb, res->cols[0].validity, (uint64_t) n);
       res->cols[0].null_count = -1;
-      ldb_dev_free(ctx, vb);
    }
    LDB_HIP(hipGetLastError());
-   *out = res;
+   *out = res.release();
    return LDB_OK;
 }

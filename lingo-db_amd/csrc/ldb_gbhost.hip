@@ -378,23 +378,6 @@ static int32_t gb_str_arg(const ldb_rel* in, const ldb_agg_spec& sp, int32_t a, 
    return LDB_OK;
 }
 
-namespace {
-struct GbRelHold {
-   ldb_ctx* ctx;
-   ldb_rel* r = nullptr;
-   ~GbRelHold() {
-      if (r) ldb_gpu_rel_release(ctx, r);
-   }
-};
-struct GbTabHold {
-   ldb_ctx* ctx;
-   ldb_table* t = nullptr;
-   ~GbTabHold() {
-      if (t) ldb_gpu_table_release(ctx, t);
-   }
-};
-} // namespace
-
 // The Join Order Benchmark's aggregate: no keys, MIN / MAX over strings (possibly beside other aggregates).  The filter runs first, the other
 // aggregates go through the key-less path below on the filtered relation, all string aggregates through ldb_str_minmax together; each
 // winning row is a one-row selection whose string the ordinary gather writes (a lazy dictionary column stays codes + dictionary until
@@ -402,7 +385,7 @@ struct GbTabHold {
 static int32_t gb_keyless_strings(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_desc* preds, int32_t n_preds, const ldb_agg_spec* aggs, int32_t n_aggs, const std::vector<bool>& is_str,
                                   const std::vector<ldb_colref>& refs, ldb_table** out) {
    LDB_TRY(ldb_rel_force(ctx, in));
-   GbRelHold filtered{ctx};
+   LdbRelHold filtered(ctx);
    ldb_rel* cur = in;
    if (n_preds > 0) {
       LDB_TRY(ldb_gpu_scan_filter(ctx, in, preds, n_preds, &filtered.r));
@@ -424,7 +407,7 @@ static int32_t gb_keyless_strings(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_de
       scols.push_back(ref);
       smax.push_back(aggs[a].fn == LDB_AGG_MAX ? 1 : 0);
    }
-   GbTabHold part{ctx}, res{ctx};
+   LdbTableHold part(ctx), res(ctx);
    if (!rest.empty()) LDB_TRY(ldb_gpu_groupby(ctx, cur, nullptr, 0, nullptr, 0, rest.data(), (int32_t) rest.size(), 1, &part.t));
    LdbBufs bufs(ctx);
    std::vector<uint32_t*> sels(scols.size(), nullptr);
@@ -439,7 +422,7 @@ static int32_t gb_keyless_strings(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_de
    for (int32_t a = 0; a < n_aggs; a++) {
       ldb_column& c = res.t->cols[(size_t) a];
       if (is_str[(size_t) a]) {
-         GbRelHold one{ctx};
+         LdbRelHold one(ctx);
          bufs.keep(sels[at_str]); // (ldb_rel_select takes the selection over)
          LDB_TRY(ldb_rel_select(ctx, cur, sels[at_str], 1, &one.r));
          for (auto& s : one.r->sides) s.may_null = true; // no non-NULL argument: the selection holds LDB_NULL_ROW and the result is NULL
@@ -457,8 +440,7 @@ static int32_t gb_keyless_strings(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_de
       snprintf(nm, sizeof(nm), "agg%d", a);
       c.name = nm;
    }
-   *out = res.t;
-   res.t = nullptr;
+   *out = res.release();
    return LDB_OK;
 }
 
@@ -531,7 +513,7 @@ extern "C" int32_t ldb_gpu_groupby(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_d
    };
 
    // output table layout: keys then aggregates
-   auto res = std::make_unique<ldb_table>();
+   LdbTableHold res(ctx, new ldb_table());
    res->ctx = ctx;
    res->name = "groupby";
    h->n_outs = n_aggs;
@@ -752,6 +734,7 @@ extern "C" int32_t ldb_gpu_groupby(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_d
    void* direct_keys = nullptr; // the output key column where the kernel writes it itself (direct slots; sorted keys with dense_keys)
    const ldb_column* direct_src = nullptr;
    uint32_t* chunk_off = nullptr;
+   LdbBufs sorted_tmp(ctx); // the sorted path's chunk counts / offsets
    uint64_t sorted_groups = 0, sorted_chunks = 0; // dense_sorted: number of groups / of 64-row chunks
    uint64_t* d_sorted_groups = nullptr; // the same count on the device (an arena word)
    const bool gb_sorted = ldb_option("gb_sorted", 1) != 0;
@@ -762,8 +745,8 @@ extern "C" int32_t ldb_gpu_groupby(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_d
       if (sorted) {
          const int64_t n_chunks = (in->n_rows + 63) / 64;
          uint32_t* chunk_cnt;
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &chunk_cnt, 4 * (size_t) n_chunks));
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &chunk_off, 4 * (size_t) n_chunks));
+         LDB_TRY(sorted_tmp.alloc(&chunk_cnt, 4 * (size_t) n_chunks));
+         LDB_TRY(sorted_tmp.alloc(&chunk_off, 4 * (size_t) n_chunks));
          LdbDesc<DGroupBy> dh_desc(ctx);
          LDB_TRY(dh_desc.upload(h, sizeof(*h)));
          DGroupBy* dh = dh_desc.p;
@@ -786,7 +769,7 @@ extern "C" int32_t ldb_gpu_groupby(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_d
          uint64_t groups = 0;
          LDB_TRY(ldb_read_u64(ctx, d_groups, &groups));
          dh_desc.release();
-         ldb_dev_free(ctx, chunk_cnt);
+         sorted_tmp.free(chunk_cnt);
          h->dense_sorted = 1;
          h->ordered_slots = 0;
          h->chunk_off = (uint64_t) chunk_off;
@@ -850,20 +833,7 @@ extern "C" int32_t ldb_gpu_groupby(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_d
    std::vector<void*> out_vals((size_t) n_aggs, nullptr);
    std::vector<uint8_t*> out_valid((size_t) n_aggs, nullptr);
    std::vector<uint8_t*> bitmaps((size_t) n_aggs, nullptr);
-   auto drop_outputs = [&]() {
-      ldb_dev_free(ctx, rep_rows);
-      rep_rows = nullptr;
-      ldb_dev_free(ctx, direct_keys);
-      direct_keys = nullptr;
-      for (int32_t a = 0; a < n_aggs; a++) {
-         ldb_dev_free(ctx, out_vals[(size_t) a]);
-         ldb_dev_free(ctx, out_valid[(size_t) a]);
-         ldb_dev_free(ctx, bitmaps[(size_t) a]);
-         out_vals[(size_t) a] = nullptr;
-         out_valid[(size_t) a] = nullptr;
-         bitmaps[(size_t) a] = nullptr;
-      }
-   };
+   LdbBufs outs(ctx); // the output buffers: the survivors are kept into the result table, a failed attempt's are freed as a whole
    for (;;) {
       h->g_cap = cap;
       h->kmult = h->ordered_slots ? (uint64_t) ((((unsigned __int128) cap) << 32) / key_range) : 0;
@@ -885,11 +855,11 @@ extern "C" int32_t ldb_gpu_groupby(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_d
          h->cross_flags = (uint64_t) cross;
       }
       if (h->direct || h->dense_keys) {
-         LDB_TRY(ldb_dev_alloc(ctx, &direct_keys, (size_t) h->direct_key_width * (size_t) max_groups));
+         LDB_TRY(outs.alloc(&direct_keys, (size_t) h->direct_key_width * (size_t) max_groups));
          h->direct_keys_out = (uint64_t) direct_keys;
       }
       if (!h->direct && h->dense_keys != 2) {
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &rep_rows, 4 * (size_t) max_groups));
+         LDB_TRY(outs.alloc(&rep_rows, 4 * (size_t) max_groups));
          h->rep_rows_out = (uint64_t) rep_rows;
          // ordered slots give up on long probe runs, which depends on the insertion order: should a REPLAYED execution
          // (ldb_readback) meet that where the recorded one did not, its group count is too high until the trace ends and the
@@ -897,12 +867,12 @@ extern "C" int32_t ldb_gpu_groupby(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_d
          if (h->ordered_slots && ctx->trace_mode == 2) LDB_HIP(hipMemsetAsync(rep_rows, 0, 4 * (size_t) max_groups, ctx->stream));
       }
       for (int32_t a = 0; a < n_aggs; a++) {
-         LDB_TRY(ldb_dev_alloc(ctx, &out_vals[(size_t) a], (size_t) oinfo[(size_t) a].width * (size_t) max_groups));
+         LDB_TRY(outs.alloc(&out_vals[(size_t) a], (size_t) oinfo[(size_t) a].width * (size_t) max_groups));
          h->outs[a].out_values = (uint64_t) out_vals[(size_t) a];
          h->outs[a].out_valid = 0;
          if (h->outs[a].cnt_acc >= 0 || h->outs[a].cnt_rows_acc >= 0 || h->outs[a].fn == LDB_AGG_ANY) {
-            LDB_TRY(ldb_dev_alloc(ctx, (void**) &out_valid[(size_t) a], (size_t) max_groups));
-            LDB_TRY(ldb_dev_alloc(ctx, (void**) &bitmaps[(size_t) a], (size_t) ((max_groups + 7) / 8 + 1)));
+            LDB_TRY(outs.alloc(&out_valid[(size_t) a], (size_t) max_groups));
+            LDB_TRY(outs.alloc(&bitmaps[(size_t) a], (size_t) ((max_groups + 7) / 8 + 1)));
             h->outs[a].out_valid = (uint64_t) out_valid[(size_t) a];
          }
       }
@@ -923,14 +893,14 @@ extern "C" int32_t ldb_gpu_groupby(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_d
          const uint32_t nparts = (uint32_t) (cap >> GBP_SHIFT);
          const uint32_t g0 = (uint32_t) std::max<int64_t>(1, std::min<int64_t>((int64_t) ctx->cus, (in->n_rows + 16383) / 16384));
          const uint64_t rows_per_wg = ((uint64_t) in->n_rows + g0 - 1) / g0;
-         uint32_t *hist = nullptr, *offs = nullptr, *slots = nullptr;
          const size_t hn = (size_t) nparts * g0;
+         LdbBufs tmpb(ctx);
+         uint32_t* slots;
          if (ldb_option("gb_partition_wc", 1) != 0 && nparts > 64) {
             // write-combining two-pass partition (ldb_wc.hip): the slots are written once as a dense array, tile-sorted by
             // partition in LDS and stored in full-line runs — the one-pass scatter below keeps nparts open 4-byte streams per
             // workgroup (Q13: 1 024), most of whose lines leave the L2 half written (2.4 ms for 148 M rows)
             uint32_t *raw, *part = nullptr, chunks = 1;
-            LdbBufs tmpb(ctx);
             LDB_TRY(tmpb.alloc(&raw, 4 * (size_t) in->n_rows));
             LDB_TRY(tmpb.alloc(&slots, 4 * (size_t) in->n_rows));
             {
@@ -938,35 +908,32 @@ extern "C" int32_t ldb_gpu_groupby(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_d
                hipLaunchKernelGGL(k_gbp_slots, dim3(ldb_grid_for(ctx, in->n_rows, 256, 8)), dim3(256), 0, ctx->stream, (const DGroupBy*) d, raw);
             }
             LDB_TRY(ldb_wc_partition(ctx, raw, nullptr, (uint64_t) in->n_rows, 0u, (uint32_t) (cap - 1), GBP_SHIFT, nparts, slots, nullptr, &part, &chunks, "k_gbp_hist", "k_gbp_scatter"));
+            tmpb.adopt(part);
             {
                LdbProf prof_(ctx, "k_gbp_count");
                hipLaunchKernelGGL(k_gbp_count, dim3(nparts), dim3(GBP_BLOCK), 0, ctx->stream, (const uint32_t*) slots, (const uint32_t*) part, chunks, nparts, (uint64_t) in->n_rows,
                                   ga + (uint64_t) h->direct_word * cap);
             }
-            ldb_dev_free(ctx, part);
-            slots = nullptr; // (owned by tmpb)
          } else {
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &hist, 4 * hn));
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &offs, 4 * hn));
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &slots, 4 * (size_t) in->n_rows));
-         {
-            LdbProf prof_(ctx, "k_gbp_hist");
-            hipLaunchKernelGGL(k_gbp_hist, dim3(g0), dim3(GBP_SBLOCK), 0, ctx->stream, (const DGroupBy*) d, nparts, rows_per_wg, hist);
+            uint32_t *hist, *offs;
+            LDB_TRY(tmpb.alloc(&hist, 4 * hn));
+            LDB_TRY(tmpb.alloc(&offs, 4 * hn));
+            LDB_TRY(tmpb.alloc(&slots, 4 * (size_t) in->n_rows));
+            {
+               LdbProf prof_(ctx, "k_gbp_hist");
+               hipLaunchKernelGGL(k_gbp_hist, dim3(g0), dim3(GBP_SBLOCK), 0, ctx->stream, (const DGroupBy*) d, nparts, rows_per_wg, hist);
+            }
+            LDB_TRY(ldb_exclusive_scan_u32(ctx, hist, offs, (int64_t) hn, nullptr));
+            {
+               LdbProf prof_(ctx, "k_gbp_scatter");
+               hipLaunchKernelGGL(k_gbp_scatter, dim3(g0), dim3(GBP_SBLOCK), 0, ctx->stream, (const DGroupBy*) d, nparts, rows_per_wg, (const uint32_t*) offs, slots);
+            }
+            {
+               LdbProf prof_(ctx, "k_gbp_count");
+               hipLaunchKernelGGL(k_gbp_count, dim3(nparts), dim3(GBP_BLOCK), 0, ctx->stream, (const uint32_t*) slots, (const uint32_t*) offs, g0, nparts, (uint64_t) in->n_rows,
+                                  ga + (uint64_t) h->direct_word * cap);
+            }
          }
-         LDB_TRY(ldb_exclusive_scan_u32(ctx, hist, offs, (int64_t) hn, nullptr));
-         {
-            LdbProf prof_(ctx, "k_gbp_scatter");
-            hipLaunchKernelGGL(k_gbp_scatter, dim3(g0), dim3(GBP_SBLOCK), 0, ctx->stream, (const DGroupBy*) d, nparts, rows_per_wg, (const uint32_t*) offs, slots);
-         }
-         {
-            LdbProf prof_(ctx, "k_gbp_count");
-            hipLaunchKernelGGL(k_gbp_count, dim3(nparts), dim3(GBP_BLOCK), 0, ctx->stream, (const uint32_t*) slots, (const uint32_t*) offs, g0, nparts, (uint64_t) in->n_rows,
-                               ga + (uint64_t) h->direct_word * cap);
-         }
-         }
-         ldb_dev_free(ctx, hist);
-         ldb_dev_free(ctx, offs);
-         ldb_dev_free(ctx, slots);
       } else if (part_values) {
          // any aggregates over direct slots too many for the caches, many rows: partition (slot, row) pairs, aggregate every slot range in LDS
          const uint32_t nparts = (uint32_t) (cap >> pv_shift);
@@ -980,12 +947,12 @@ extern "C" int32_t ldb_gpu_groupby(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_d
             hipLaunchKernelGGL(k_gbp_slots, dim3(ldb_grid_for(ctx, in->n_rows, 256, 8)), dim3(256), 0, ctx->stream, (const DGroupBy*) d, raw);
          }
          LDB_TRY(ldb_wc_partition(ctx, raw, nullptr, (uint64_t) in->n_rows, 0u, (uint32_t) (cap - 1), pv_shift, nparts, slots, prow, &part, &chunks, "k_gbp_hist", "k_gbp_scatter"));
+         tmpb.adopt(part);
          {
             LdbProf prof_(ctx, "k_gbp_agg");
             hipLaunchKernelGGL(k_gbp_agg, dim3(nparts), dim3(GBP_BLOCK), (size_t) 8 * (size_t) nw << pv_shift, ctx->stream, (const DGroupBy*) d, (const uint32_t*) slots, (const uint32_t*) prow,
                                (const uint32_t*) part, chunks, nparts, (uint64_t) in->n_rows, pv_shift);
          }
-         ldb_dev_free(ctx, part);
       } else if (in->n_rows) {
          int per_cu = lds_bytes > 40 * 1024 ? 2 : 4;
          // (the sorted, LDS-free path was swept over 2 / 3 / 4 / 6 / 8 resident workgroups per CU: 5.52 / 4.22 / 3.90 / 3.70 / 3.83 ms on one box, but 6 gave 4.05 ms on the
@@ -1022,8 +989,9 @@ extern "C" int32_t ldb_gpu_groupby(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_d
       } else {
          LdbProf prof_(ctx, "k_gb_finalize");
          const int64_t n_chunks = (int64_t) ((cap + 63) / 64);
+         LdbBufs fin(ctx);
          uint32_t *pop = nullptr, *off;
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &off, 4 * (size_t) n_chunks));
+         LDB_TRY(fin.alloc(&off, 4 * (size_t) n_chunks));
          const int fgrid = ldb_grid_for(ctx, (int64_t) cap, 256, 8);
          const uint64_t* occ = h->direct ? (const uint64_t*) h->g_acc + (uint64_t) h->direct_word * cap : (const uint64_t*) h->g_keys;
          if (ldb_option("scan_single_pass", 1) != 0) { // occupied slots per chunk + their exclusive scan + the group count: one chained launch
@@ -1034,7 +1002,7 @@ extern "C" int32_t ldb_gpu_groupby(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_d
                                c.epoch);
             if (hipGetLastError() != hipSuccess) return ldb_chain_failed(ctx);
          } else {
-            LDB_TRY(ldb_dev_alloc(ctx, (void**) &pop, 4 * (size_t) n_chunks));
+            LDB_TRY(fin.alloc(&pop, 4 * (size_t) n_chunks));
             hipLaunchKernelGGL(k_gb_occupancy, dim3(fgrid), dim3(256), 0, ctx->stream, occ, cap, pop);
             LDB_TRY(ldb_exclusive_scan_u32(ctx, pop, off, n_chunks, (uint64_t*) (d_ctl + 1)));
          }
@@ -1044,8 +1012,6 @@ extern "C" int32_t ldb_gpu_groupby(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_d
                hipLaunchKernelGGL(k_pack_valid_bytes, dim3(ldb_grid_for(ctx, (int64_t) max_groups, 256 * 8, 4)), dim3(256), 0, ctx->stream, out_valid[(size_t) a], bitmaps[(size_t) a],
                                   (const unsigned long long*) (d_ctl + 1), (uint64_t) max_groups, d_ctl + 2 + a);
          LDB_HIP(hipGetLastError());
-         ldb_dev_free(ctx, pop);
-         ldb_dev_free(ctx, off);
       }
       static_assert(sizeof(ctl) <= 64 * sizeof(int64_t), "control block must fit the pinned scratch words");
       LDB_TRY(LDB_READBACK(ctx, ctl, d_ctl, ctl_bytes));
@@ -1053,25 +1019,24 @@ extern "C" int32_t ldb_gpu_groupby(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_d
       d_desc.release();
       const uint64_t flags = (uint64_t) ctl[0];
       if ((flags & 3) == 0) break;
-      drop_outputs();
+      outs.free_all();
+      rep_rows = nullptr;
+      direct_keys = nullptr;
+      out_vals.assign((size_t) n_aggs, nullptr);
+      out_valid.assign((size_t) n_aggs, nullptr);
+      bitmaps.assign((size_t) n_aggs, nullptr);
       if ((flags & 2) && h->ordered_slots) { // long probe runs: this key distribution needs hashed slots
          h->ordered_slots = 0;
          in->sides[(size_t) keys[0].side].table->cols[(size_t) keys[0].col].skewed = true;
          if ((flags & 1) == 0) continue;
       }
       // global table overflowed: retry larger (the estimate was too low)
-      if (cap >= cap_max) {
-         ldb_dev_free(ctx, chunk_off);
-         LDB_FAIL(LDB_ERR_HIP, "groupby: global table overflow at maximum capacity");
-      }
+      if (cap >= cap_max) LDB_FAIL(LDB_ERR_HIP, "groupby: global table overflow at maximum capacity");
       cap = std::min(cap * 8, cap_max);
    }
-   ldb_dev_free(ctx, chunk_off);
+   sorted_tmp.free(chunk_off);
    n_groups = (uint64_t) ctl[1];
-   for (int32_t a = 0; a < n_aggs; a++) {
-      ldb_dev_free(ctx, out_valid[(size_t) a]);
-      out_valid[(size_t) a] = nullptr;
-   }
+   for (int32_t a = 0; a < n_aggs; a++) outs.free(out_valid[(size_t) a]);
 
    // ---- result table: key columns = gather of representative rows, then aggregates
    res->n_rows = (int64_t) n_groups;
@@ -1082,6 +1047,7 @@ extern "C" int32_t ldb_gpu_groupby(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_d
       kc.type = direct_src->type;
       kc.width = direct_src->width;
       kc.values = direct_keys;
+      outs.keep(direct_keys);
       kc.value_bytes = (int64_t) n_groups * kc.width;
       kc.owned = true;
       if (direct_src->has_range) { // the groups' keys are values of the source column: its cached range stays a valid superset
@@ -1089,14 +1055,12 @@ extern "C" int32_t ldb_gpu_groupby(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_d
          kc.vmin = direct_src->vmin;
          kc.vmax = direct_src->vmax;
       }
-      ldb_dev_free(ctx, rep_rows); // (sorted keys with an ANY aggregate: the representative rows were only read by the finalisation)
-      rep_rows = nullptr;
+      outs.free(rep_rows); // (sorted keys with an ANY aggregate: the representative rows were only read by the finalisation)
    } else {
-      ldb_rel* reps = nullptr;
-      LDB_TRY(ldb_rel_select(ctx, in, rep_rows, (int64_t) n_groups, &reps));
-      const int32_t s = n_keys ? ldb_gather_columns(ctx, reps, keys, n_keys, res->cols.data()) : LDB_OK;
-      ldb_gpu_rel_release(ctx, reps);
-      if (s != LDB_OK) return s;
+      LdbRelHold reps(ctx);
+      outs.keep(rep_rows); // (ldb_rel_select takes the selection over)
+      LDB_TRY(ldb_rel_select(ctx, in, rep_rows, (int64_t) n_groups, &reps.r));
+      if (n_keys) LDB_TRY(ldb_gather_columns(ctx, reps.r, keys, n_keys, res->cols.data()));
    }
    for (int32_t a = 0; a < n_aggs; a++) {
       ldb_column& c = res->cols[(size_t) (n_keys + a)];
@@ -1106,6 +1070,7 @@ extern "C" int32_t ldb_gpu_groupby(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_d
       c.type = oinfo[(size_t) a].type;
       c.width = oinfo[(size_t) a].width;
       c.values = out_vals[(size_t) a];
+      outs.keep(c.values);
       c.value_bytes = (int64_t) n_groups * c.width;
       c.owned = true;
       if (is_str[(size_t) a]) { // a LAZY utf8 column (ldb_column_is_lazy): the codes the kernels wrote + the argument column's dictionary
@@ -1125,9 +1090,10 @@ extern "C" int32_t ldb_gpu_groupby(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_d
          const int64_t nulls = (int64_t) ctl[2 + a];
          if (nulls) {
             c.validity = bitmaps[(size_t) a];
+            outs.keep(c.validity);
             c.null_count = nulls;
          } else {
-            ldb_dev_free(ctx, bitmaps[(size_t) a]);
+            outs.free(bitmaps[(size_t) a]);
          }
       }
    }

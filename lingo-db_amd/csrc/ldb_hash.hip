@@ -78,24 +78,23 @@ extern "C" int32_t ldb_gpu_map_column(ldb_ctx* ctx, ldb_rel* in, ldb_colref col,
    if (dc.type != LDB_T_DATE32) LDB_FAIL(LDB_ERR_INVALID, "map_column: extract(year) needs a date32 column");
    ldb_coltype t = {LDB_T_INT64, 0, 0, 0};
    const char* nm = name ? name : "year";
-   ldb_table* res;
-   LDB_TRY(ldb_gpu_table_alloc(ctx, "mapped", 1, &t, &nm, in->n_rows, nullptr, 0, &res));
+   LdbTableHold res(ctx);
+   LDB_TRY(ldb_gpu_table_alloc(ctx, "mapped", 1, &t, &nm, in->n_rows, nullptr, 0, &res.t));
    const int64_t n = in->n_rows;
    const bool nullable = dc.validity || dc.rowids;
+   LdbBufs tmp(ctx);
    uint8_t* vb = nullptr;
-   if (nullable) LDB_TRY(ldb_dev_alloc(ctx, (void**) &vb, (size_t) (n ? n : 1)));
+   if (nullable) LDB_TRY(tmp.alloc(&vb, (size_t) (n ? n : 1)));
    const int grid = ldb_grid_for(ctx, n, 256, 8);
    if (n) hipLaunchKernelGGL(k_map_column, dim3(grid), dim3(256), 0, ctx->stream, dc, fn, (uint64_t) n, (int64_t*) res->cols[0].values, vb);
    if (nullable) { // NULL in → NULL out
-      uint8_t* bm;
-      LDB_TRY(ldb_dev_alloc(ctx, (void**) &bm, (size_t) ((n + 7) / 8 + 1)));
+      LDB_TRY(LdbBufs::alloc_into(ctx, &res->cols[0].validity, (size_t) ((n + 7) / 8 + 1)));
+      uint8_t* bm = res->cols[0].validity;
       if (n) hipLaunchKernelGGL(k_pack_bytes_to_bits, dim3(grid), dim3(256), 0, ctx->stream, (const uint8_t*) vb, bm, (uint64_t) n);
-      res->cols[0].validity = bm;
       res->cols[0].null_count = -1; // unknown (Arrow convention)
-      ldb_dev_free(ctx, vb);
    }
    LDB_HIP(hipGetLastError());
-   *out = res;
+   *out = res.release();
    return LDB_OK;
 }
 
@@ -133,23 +132,23 @@ extern "C" int32_t ldb_gpu_map_muldiv(ldb_ctx* ctx, ldb_rel* in, ldb_colref num,
    if (!numeric(dn) || !numeric(dd)) LDB_FAIL(LDB_ERR_INVALID, "map_muldiv: decimal or integer columns expected");
    ldb_coltype t = {LDB_T_DECIMAL128, out_precision, out_scale, 0};
    const char* nm = name ? name : "ratio";
-   ldb_table* res;
-   LDB_TRY(ldb_gpu_table_alloc(ctx, "mapped", 1, &t, &nm, in->n_rows, nullptr, 0, &res));
+   LdbTableHold res(ctx);
+   LDB_TRY(ldb_gpu_table_alloc(ctx, "mapped", 1, &t, &nm, in->n_rows, nullptr, 0, &res.t));
    const int64_t n = in->n_rows;
-   uint8_t *vb, *bm;
-   LDB_TRY(ldb_dev_alloc(ctx, (void**) &vb, (size_t) (n ? n : 1)));
-   LDB_TRY(ldb_dev_alloc(ctx, (void**) &bm, (size_t) ((n + 7) / 8 + 1)));
+   LdbBufs tmp(ctx);
+   uint8_t* vb;
+   LDB_TRY(tmp.alloc(&vb, (size_t) (n ? n : 1)));
+   LDB_TRY(LdbBufs::alloc_into(ctx, &res->cols[0].validity, (size_t) ((n + 7) / 8 + 1)));
+   uint8_t* bm = res->cols[0].validity;
    const int grid = ldb_grid_for(ctx, n, 256, 8);
    const i128 mul = (i128) (((u128) (uint64_t) mul_hi << 64) | (uint64_t) mul_lo);
    if (n) {
       hipLaunchKernelGGL(k_map_muldiv, dim3(grid), dim3(256), 0, ctx->stream, dn, dd, mul, (int) mul_div_pow10, (int) pow10, (uint64_t) n, (i128*) res->cols[0].values, vb);
       hipLaunchKernelGGL(k_pack_bytes_to_bits, dim3(grid), dim3(256), 0, ctx->stream, (const uint8_t*) vb, bm, (uint64_t) n);
    }
-   res->cols[0].validity = bm;
    res->cols[0].null_count = -1; // unknown (Arrow convention)
-   ldb_dev_free(ctx, vb);
    LDB_HIP(hipGetLastError());
-   *out = res;
+   *out = res.release();
    return LDB_OK;
 }
 
@@ -160,18 +159,10 @@ extern "C" int32_t ldb_gpu_rel_zip(ldb_ctx* ctx, ldb_rel* in, const ldb_table* t
    LDB_TRY(ldb_rel_force(ctx, in));
    if (t->n_rows != in->n_rows) LDB_FAIL(LDB_ERR_INVALID, "rel_zip: table has %ld rows, relation %ld", (long) t->n_rows, (long) in->n_rows);
    if (in->sides.size() + 1 > LDB_MAX_SIDES) LDB_FAIL(LDB_ERR_UNSUPPORTED, "rel_zip: more than %d sides (materialize first)", LDB_MAX_SIDES);
-   ldb_rel* r = ldb_rel_new(ctx);
+   LdbRelHold r(ctx, ldb_rel_new(ctx));
    r->n_rows = in->n_rows;
-   for (auto& s : in->sides) {
-      ldb_rel_side ns{s.table, nullptr, false, s.may_null};
-      if (s.rowids) {
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &ns.rowids, 4 * (size_t) (in->n_rows ? in->n_rows : 1)));
-         if (in->n_rows) LDB_HIP(hipMemcpyAsync(ns.rowids, s.rowids, 4 * (size_t) in->n_rows, hipMemcpyDeviceToDevice, ctx->stream));
-         ns.owned = true;
-      }
-      r->sides.push_back(ns);
-   }
+   LDB_TRY(ldb_rel_copy_sides(r.r, in));
    r->sides.push_back(ldb_rel_side{t, nullptr, false});
-   *out = r;
+   *out = r.release();
    return LDB_OK;
 }

@@ -298,6 +298,23 @@ struct LdbBufs {
       *out = (T*) p;
       return LDB_OK;
    }
+   // a block that a long-lived object under a holder of its own owns from the start (a column of a held table, a side of a held relation)
+   template <typename T>
+   static int32_t alloc_into(ldb_ctx* ctx, T** field, size_t bytes) {
+      LdbBufs b(ctx);
+      LDB_TRY(b.alloc(field, bytes));
+      b.keep(*field);
+      return LDB_OK;
+   }
+   // such an object gives a block up (a validity bitmap that turned out all-valid, a buffer about to be replaced)
+   template <typename T>
+   static void drop(ldb_ctx* ctx, T** field) {
+      ldb_dev_free(ctx, *field);
+      *field = nullptr;
+   }
+   void adopt(void* p) { // a block somebody else allocated becomes this scope's
+      if (p) ptrs.push_back(p);
+   }
    void keep(void* p) { // the caller takes the block over (it outlives the call)
       for (size_t i = 0; i < ptrs.size(); i++)
          if (ptrs[i] == p) {
@@ -305,7 +322,70 @@ struct LdbBufs {
             return;
          }
    }
+   void free(void* p) { // free now (before a later allocation of the same call) and forget the block; a block not listed is left alone
+      const size_t before = ptrs.size();
+      keep(p);
+      if (ptrs.size() != before) ldb_dev_free(ctx, p);
+   }
+   void free_all() {
+      for (void* p : ptrs) ldb_dev_free(ctx, p);
+      ptrs.clear();
+   }
 };
+
+// a relation / table under construction: released when the scope ends unless release() handed it to the caller
+struct LdbRelHold {
+   ldb_ctx* ctx;
+   ldb_rel* r = nullptr;
+   explicit LdbRelHold(ldb_ctx* c, ldb_rel* rel = nullptr) : ctx(c), r(rel) {}
+   LdbRelHold(const LdbRelHold&) = delete;
+   LdbRelHold& operator=(const LdbRelHold&) = delete;
+   ~LdbRelHold() {
+      if (r) ldb_gpu_rel_release(ctx, r);
+   }
+   ldb_rel* operator->() const { return r; }
+   ldb_rel* release() {
+      ldb_rel* x = r;
+      r = nullptr;
+      return x;
+   }
+};
+struct LdbTableHold {
+   ldb_ctx* ctx;
+   ldb_table* t = nullptr;
+   explicit LdbTableHold(ldb_ctx* c, ldb_table* tab = nullptr) : ctx(c), t(tab) {}
+   LdbTableHold(const LdbTableHold&) = delete;
+   LdbTableHold& operator=(const LdbTableHold&) = delete;
+   ~LdbTableHold() {
+      if (t) ldb_gpu_table_release(ctx, t);
+   }
+   ldb_table* operator->() const { return t; }
+   ldb_table* release() {
+      ldb_table* x = t;
+      t = nullptr;
+      return x;
+   }
+};
+// appends a side with a new, owned row-id vector of n entries to r (r owns the vector from here on)
+static inline int32_t ldb_rel_push_side(ldb_rel* r, const ldb_table* table, bool may_null, size_t n, uint32_t** rowids) {
+   LDB_TRY(LdbBufs::alloc_into(r->ctx, rowids, 4 * (n ? n : 1)));
+   r->sides.push_back(ldb_rel_side{table, *rowids, true, may_null});
+   return LDB_OK;
+}
+// appends src's sides to r for the same rows in the same order: identity sides as they are, row-id vectors copied
+static inline int32_t ldb_rel_copy_sides(ldb_rel* r, const ldb_rel* src) {
+   const size_t n = (size_t) src->n_rows;
+   for (auto& s : src->sides) {
+      if (!s.rowids) {
+         r->sides.push_back(ldb_rel_side{s.table, nullptr, false, s.may_null});
+         continue;
+      }
+      uint32_t* ids;
+      LDB_TRY(ldb_rel_push_side(r, s.table, s.may_null, n, &ids));
+      if (n) LDB_HIP(hipMemcpyAsync(ids, s.rowids, 4 * n, hipMemcpyDeviceToDevice, r->ctx->stream));
+   }
+   return LDB_OK;
+}
 
 // a descriptor uploaded for one call (ldb_dev_upload): its reference on the descriptor cache — or its block, when it was not cacheable — is
 // given back when the scope ends, error returns included, so an entry no operator uses any more can always be evicted (desc_cache_mb stays

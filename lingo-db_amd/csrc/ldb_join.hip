@@ -418,21 +418,22 @@ __global__ void k_radix_locality(DRadix d, uint64_t stride, unsigned int* __rest
    }
 }
 
-struct RadixProbe { // the clustered stand-in for a probe relation
+struct RadixProbe { // the clustered stand-in for a probe relation; owns what radix_prepare made
+   ldb_ctx* ctx;
    ldb_rel* rel = nullptr; // sides: [keys table (identity)] + the probe's sides through the permutation
    ldb_table* keys = nullptr;
    // rank-table probes whose partitions are LDS-sized: where partition q begins (part_offs[q * chunks]) and what it covers
    uint32_t* part_offs = nullptr;
    uint32_t chunks = 0, nparts = 0, shift = 0;
+   explicit RadixProbe(ldb_ctx* c) : ctx(c) {}
+   RadixProbe(const RadixProbe&) = delete;
+   RadixProbe& operator=(const RadixProbe&) = delete;
+   ~RadixProbe() {
+      if (rel) ldb_gpu_rel_release(ctx, rel);
+      if (keys) ldb_gpu_table_release(ctx, keys);
+      ldb_dev_free(ctx, part_offs);
+   }
 };
-static void radix_release(ldb_ctx* ctx, RadixProbe& rp) {
-   if (rp.rel) ldb_gpu_rel_release(ctx, rp.rel);
-   if (rp.keys) ldb_gpu_table_release(ctx, rp.keys);
-   ldb_dev_free(ctx, rp.part_offs);
-   rp.rel = nullptr;
-   rp.keys = nullptr;
-   rp.part_offs = nullptr;
-}
 
 // ---------------------------------------------------------------- LDS-staged probe of a radix-partitioned probe side
 // North star: "radix-partitioned hash-join build/probe … LDS-staged hash buckets".  After the write-combining partition
@@ -574,9 +575,10 @@ static int32_t radix_prepare(ldb_ctx* ctx, ldb_hashtable* ht, ldb_rel* probe, co
    d.pshift = lg - lp;
    d.grid = (uint32_t) std::min<int64_t>(ctx->cus * 8, (n + 4095) / 4096);
    d.rows_per_wg = ((uint64_t) n + d.grid - 1) / d.grid;
-   uint32_t *hist = nullptr, *offs = nullptr, *perm;
    const size_t hn = (size_t) nparts * d.grid;
-   LDB_TRY(ldb_dev_alloc(ctx, (void**) &perm, 4 * (size_t) n));
+   LdbBufs tmp(ctx);
+   uint32_t* perm;
+   LDB_TRY(tmp.alloc(&perm, 4 * (size_t) n));
    ldb_coltype kt = {LDB_T_INT32, 0, 0, 0};
    kt.type = kc.type;
    const char* nm = "radix_key";
@@ -585,55 +587,50 @@ static int32_t radix_prepare(ldb_ctx* ctx, ldb_hashtable* ht, ldb_rel* probe, co
       // write-combining partition (ldb_wc.hip): tile-sort in LDS, full-line runs, two passes above 64 partitions — the
       // scatter below keeps `nparts` open 4-byte streams per workgroup and loses to the direct probe beyond ~16 partitions
       const uint32_t shift = d.pshift + (ht->direct == 2 ? 5u : 0u);
-      const int32_t st = ldb_wc_partition(ctx, (const uint32_t*) kc.values, nullptr, (uint64_t) n, (uint32_t) (int32_t) ht->kmin, (uint32_t) (ht->kmax - ht->kmin), shift, nparts,
-                                          (uint32_t*) rp.keys->cols[0].values, perm, &rp.part_offs, &rp.chunks, "k_radix_hist", "k_radix_scatter");
-      if (st != LDB_OK) {
-         ldb_dev_free(ctx, perm);
-         return st;
-      }
+      LDB_TRY(ldb_wc_partition(ctx, (const uint32_t*) kc.values, nullptr, (uint64_t) n, (uint32_t) (int32_t) ht->kmin, (uint32_t) (ht->kmax - ht->kmin), shift, nparts,
+                               (uint32_t*) rp.keys->cols[0].values, perm, &rp.part_offs, &rp.chunks, "k_radix_hist", "k_radix_scatter"));
       rp.nparts = nparts;
       rp.shift = shift;
    } else {
-   LDB_TRY(ldb_dev_alloc(ctx, (void**) &hist, 4 * hn));
-   LDB_TRY(ldb_dev_alloc(ctx, (void**) &offs, 4 * hn));
-   {
-      LdbProf prof_(ctx, "k_radix_hist");
-      hipLaunchKernelGGL(k_radix_hist, dim3(d.grid), dim3(RX_BLOCK), 0, ctx->stream, d, hist);
+      LdbBufs hb(ctx); // (gone before the sides below are allocated)
+      uint32_t *hist, *offs;
+      LDB_TRY(hb.alloc(&hist, 4 * hn));
+      LDB_TRY(hb.alloc(&offs, 4 * hn));
+      {
+         LdbProf prof_(ctx, "k_radix_hist");
+         hipLaunchKernelGGL(k_radix_hist, dim3(d.grid), dim3(RX_BLOCK), 0, ctx->stream, d, hist);
+      }
+      LDB_TRY(ldb_exclusive_scan_u32(ctx, hist, offs, (int64_t) hn, nullptr));
+      {
+         LdbProf prof_(ctx, "k_radix_scatter");
+         hipLaunchKernelGGL(k_radix_scatter, dim3(d.grid), dim3(RX_BLOCK), 0, ctx->stream, d, (const uint32_t*) offs, (uint32_t*) rp.keys->cols[0].values, perm);
+      }
+      LDB_HIP(hipGetLastError());
    }
-   LDB_TRY(ldb_exclusive_scan_u32(ctx, hist, offs, (int64_t) hn, nullptr));
-   {
-      LdbProf prof_(ctx, "k_radix_scatter");
-      hipLaunchKernelGGL(k_radix_scatter, dim3(d.grid), dim3(RX_BLOCK), 0, ctx->stream, d, (const uint32_t*) offs, (uint32_t*) rp.keys->cols[0].values, perm);
-   }
-   LDB_HIP(hipGetLastError());
-   }
-   ldb_dev_free(ctx, hist);
-   ldb_dev_free(ctx, offs);
-   ldb_rel* r = ldb_rel_new(ctx);
+   LdbRelHold r(ctx, ldb_rel_new(ctx));
    r->n_rows = n;
    r->sides.push_back(ldb_rel_side{rp.keys, nullptr, false});
    bool perm_taken = false;
    const int cg = ldb_grid_for(ctx, n, 256, 8);
    for (auto& s : probe->sides) {
-      ldb_rel_side ns{s.table, nullptr, true, s.may_null};
       if (!s.rowids && !perm_taken) {
-         ns.rowids = perm;
+         r->sides.push_back(ldb_rel_side{s.table, perm, true, s.may_null});
+         tmp.keep(perm);
          perm_taken = true;
       } else {
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &ns.rowids, 4 * (size_t) n));
-         hipLaunchKernelGGL(k_compose_null, dim3(cg), dim3(256), 0, ctx->stream, (const uint32_t*) s.rowids, (const uint32_t*) perm, ns.rowids, (uint64_t) n);
+         uint32_t* ids;
+         LDB_TRY(ldb_rel_push_side(r.r, s.table, s.may_null, (size_t) n, &ids));
+         hipLaunchKernelGGL(k_compose_null, dim3(cg), dim3(256), 0, ctx->stream, (const uint32_t*) s.rowids, (const uint32_t*) perm, ids, (uint64_t) n);
       }
-      r->sides.push_back(ns);
    }
-   if (!perm_taken) ldb_dev_free(ctx, perm);
    LDB_HIP(hipGetLastError());
-   rp.rel = r;
+   rp.rel = r.release();
    return LDB_OK;
 }
 // drop the key-table side a clustered probe put in front of the probe's own sides
 static void radix_strip(ldb_ctx* ctx, ldb_rel* r) {
    if (r->sides.empty()) return;
-   if (r->sides[0].owned) ldb_dev_free(ctx, r->sides[0].rowids);
+   if (r->sides[0].owned) LdbBufs::drop(ctx, &r->sides[0].rowids);
    r->sides.erase(r->sides.begin());
 }
 
@@ -701,9 +698,8 @@ extern "C" int32_t ldb_gpu_join_build(ldb_ctx* ctx, ldb_rel* build, const ldb_co
       if (range0 > 0 && build_unique && ldb_option("join_direct", 1) != 0 && ldb_option("join_rank", 1) != 0 && range0 <= ((unsigned __int128) 1 << 32) &&
           (range0 <= (unsigned __int128) std::max<int64_t>(4096, 64 * build->n_rows) || range0 <= ((unsigned __int128) 1 << 26)) && got[0] >= INT32_MIN && got[1] <= INT32_MAX && build->n_rows < (int64_t) LDB_NULL_ROW) {
          const uint64_t n_words = (uint64_t) (range0 / 32) + 1;
-         uint64_t* tab = nullptr;
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &tab, 8 * (size_t) n_words));
-         ht->slots = tab; // (owned by the table object from here on: freed on every error return)
+         LDB_TRY(LdbBufs::alloc_into(ctx, &ht->slots, 8 * (size_t) n_words)); // (owned by the table object: freed on every error return)
+         uint64_t* tab = ht->slots;
          LDB_HIP(hipMemsetAsync(tab, 0, 8 * (size_t) n_words, ctx->stream));
          unsigned long long* counter;
          LDB_TRY(ldb_counters(ctx, 3, (uint64_t**) &counter));
@@ -767,14 +763,14 @@ extern "C" int32_t ldb_gpu_join_build(ldb_ctx* ctx, ldb_rel* build, const ldb_co
                cwords = (uint64_t) (range0 >> shift) / 32 + 1;
             }
             if (want) {
-               LDB_TRY(ldb_dev_alloc(ctx, (void**) &ht->coarse, 4 * (size_t) cwords));
+               LDB_TRY(LdbBufs::alloc_into(ctx, &ht->coarse, 4 * (size_t) cwords));
                ht->coarse_words = (uint32_t) cwords;
                ht->coarse_shift = shift;
                hipLaunchKernelGGL(k_rank_coarse, dim3((unsigned) ((cwords + 255) / 256)), dim3(256), 0, ctx->stream, (const uint64_t*) tab, n_words, ht->coarse, (uint32_t) cwords, shift);
                LDB_HIP(hipGetLastError());
             }
             if (!ht->rank_sorted) {
-               LDB_TRY(ldb_dev_alloc(ctx, (void**) &ht->next, 4 * (size_t) (build->n_rows ? build->n_rows : 1)));
+               LDB_TRY(LdbBufs::alloc_into(ctx, &ht->next, 4 * (size_t) (build->n_rows ? build->n_rows : 1)));
                h->next = (uint64_t) ht->next;
                LdbDesc<DJoin> dp_desc(ctx);
                LDB_TRY(dp_desc.upload(h, sizeof(*h)));
@@ -784,8 +780,7 @@ extern "C" int32_t ldb_gpu_join_build(ldb_ctx* ctx, ldb_rel* build, const ldb_co
                dp_desc.release();
             }
          } else { // duplicate keys: the promise does not hold — the general layouts below
-            ldb_dev_free(ctx, tab);
-            ht->slots = nullptr;
+            LdbBufs::drop(ctx, &ht->slots);
             h->direct = 0;
             h->slots = 0;
             h->counter = 0;
@@ -808,7 +803,7 @@ extern "C" int32_t ldb_gpu_join_build(ldb_ctx* ctx, ldb_rel* build, const ldb_co
          ht->cap = (uint64_t) range0;
          if (range0 <= ((unsigned __int128) 1 << 27) && range0 >= 4096) { // key bits: 32x smaller than the table, L2-resident for selective builds
             const size_t words = (size_t) ((range0 + 31) / 32);
-            LDB_TRY(ldb_dev_alloc(ctx, (void**) &ht->key_bits, 4 * words));
+            LDB_TRY(LdbBufs::alloc_into(ctx, &ht->key_bits, 4 * words));
             LDB_HIP(hipMemsetAsync(ht->key_bits, 0, 4 * words, ctx->stream));
          }
       } else if (got[0] <= got[1]) { // at least one non-NULL key
@@ -833,7 +828,7 @@ extern "C" int32_t ldb_gpu_join_build(ldb_ctx* ctx, ldb_rel* build, const ldb_co
          const unsigned __int128 range = (unsigned __int128) ((__int128) got[1] - got[0]) + 1;
          if (range <= ((unsigned __int128) 1 << 27)) { // <= 16 MB of bits
             const size_t words = (size_t) ((range + 31) / 32);
-            LDB_TRY(ldb_dev_alloc(ctx, (void**) &ht->key_bits, 4 * words));
+            LDB_TRY(LdbBufs::alloc_into(ctx, &ht->key_bits, 4 * words));
             LDB_HIP(hipMemsetAsync(ht->key_bits, 0, 4 * words, ctx->stream));
          }
       }
@@ -843,12 +838,11 @@ extern "C" int32_t ldb_gpu_join_build(ldb_ctx* ctx, ldb_rel* build, const ldb_co
    const bool force_chained = ldb_option("join_chained", 0) == 1; // tests
    if (force_chained && !ht->direct) {
       ht->ordered_slots = 0;
-      ldb_dev_free(ctx, ht->key_bits);
-      ht->key_bits = nullptr;
+      LdbBufs::drop(ctx, &ht->key_bits);
    }
    if (force_chained || (ht->direct && !build_unique)) { // a direct table without the promise of unique keys chains from the start
       ht->chained = 1;
-      LDB_TRY(ldb_dev_alloc(ctx, (void**) &ht->next, 4 * (size_t) (build->n_rows ? build->n_rows : 1)));
+      LDB_TRY(LdbBufs::alloc_into(ctx, &ht->next, 4 * (size_t) (build->n_rows ? build->n_rows : 1)));
    }
    // two 4-byte integer keys, open addressing: the key values live in the slot (DJoin::pair32)
    if (!ht->direct && !ht->chained && n_keys == 2 && ldb_option("join_pair32", 1) != 0) {
@@ -860,7 +854,7 @@ extern "C" int32_t ldb_gpu_join_build(ldb_ctx* ctx, ldb_rel* build, const ldb_co
       ht->pair32 = narrow ? 1 : 0;
    }
    ht->slot_bytes = (ht->direct ? 4 : ht->pair32 ? 16 : 8) * (size_t) ht->cap;
-   LDB_TRY(ldb_dev_alloc(ctx, (void**) &ht->slots, ht->slot_bytes));
+   LDB_TRY(LdbBufs::alloc_into(ctx, &ht->slots, ht->slot_bytes));
    LDB_HIP(hipMemsetAsync(ht->slots, 0, ht->slot_bytes, ctx->stream));
    h->cap = ht->cap;
    h->slots = (uint64_t) ht->slots;
@@ -896,7 +890,7 @@ extern "C" int32_t ldb_gpu_join_build(ldb_ctx* ctx, ldb_rel* build, const ldb_co
       LDB_TRY(ldb_read_u64_at(ctx, dflags, &f, LDB_SITE, LDB_RB_ORDER_DEPENDENT));
       if (ht->direct && (f & 1) && !ht->chained) { // duplicate keys in a direct table: chain them
          ht->chained = 1;
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &ht->next, 4 * (size_t) build->n_rows));
+         LDB_TRY(LdbBufs::alloc_into(ctx, &ht->next, 4 * (size_t) build->n_rows));
          LDB_HIP(hipMemsetAsync(ht->slots, 0, ht->slot_bytes, ctx->stream));
          LDB_TRY(ldb_counters(ctx, 1, (uint64_t**) &dflags));
          h->flags = (uint64_t) dflags;
@@ -905,11 +899,10 @@ extern "C" int32_t ldb_gpu_join_build(ldb_ctx* ctx, ldb_rel* build, const ldb_co
       if ((f & 2) && !ht->chained) {
          if (ht->ordered_slots) { // this key distribution needs hashed slots
             ht->ordered_slots = 0;
-            ldb_dev_free(ctx, ht->key_bits);
-            ht->key_bits = nullptr;
+            LdbBufs::drop(ctx, &ht->key_bits);
          } else { // hashed and still long runs: duplicates → chain them
             ht->chained = 1;
-            LDB_TRY(ldb_dev_alloc(ctx, (void**) &ht->next, 4 * (size_t) build->n_rows));
+            LDB_TRY(LdbBufs::alloc_into(ctx, &ht->next, 4 * (size_t) build->n_rows));
          }
          LDB_HIP(hipMemsetAsync(ht->slots, 0, ht->slot_bytes, ctx->stream));
          LDB_TRY(ldb_counters(ctx, 1, (uint64_t**) &dflags));
@@ -1008,13 +1001,11 @@ extern "C" int32_t ldb_gpu_join_probe_count(ldb_ctx* ctx, ldb_hashtable* ht, ldb
 static int32_t probe_count_impl(ldb_ctx* ctx, ldb_hashtable* ht, ldb_rel* probe, const ldb_colref* keys, int32_t n_keys, int64_t* matches, bool radix_ok, const RadixProbe* part) {
    if (!ctx || !ht || !probe || !matches) LDB_FAIL(LDB_ERR_INVALID, "join_probe_count: NULL argument");
    if (radix_ok) {
-      RadixProbe rp;
+      RadixProbe rp(ctx);
       LDB_TRY(radix_prepare(ctx, ht, probe, keys, n_keys, LDB_JOIN_INNER, rp));
       if (rp.rel) { // an unclustered probe side: partitioned by slot range first
          const ldb_colref k0 = {0, 0};
-         const int32_t st = probe_count_impl(ctx, ht, rp.rel, &k0, 1, matches, false, &rp);
-         radix_release(ctx, rp);
-         return st;
+         return probe_count_impl(ctx, ht, rp.rel, &k0, 1, matches, false, &rp);
       }
    }
    auto hp = std::make_unique<DJoin>();
@@ -1046,6 +1037,58 @@ extern "C" int32_t ldb_gpu_join_probe_residual(ldb_ctx* ctx, ldb_hashtable* ht, 
                                                const ldb_join_residual* resid, int32_t n_resid, ldb_rel** out, ldb_table** mark_out) {
    return probe_impl(ctx, ht, probe, keys, n_keys, kind, resid, n_resid, out, mark_out, true);
 }
+// the tail SEMI / ANTI and the build-side kinds share: read the count, compact the bitmap into ascending row numbers, restrict `src` to them.
+// `done` (may be NULL): the caller's temporaries, the bitmap among them, freed before the selection's sides are allocated
+static int32_t select_by_bitmap(ldb_ctx* ctx, ldb_rel* src, const uint64_t* bitmap, int64_t n_words, const void* d_count, uint32_t site, LdbBufs* done, ldb_rel** out) {
+   uint64_t total = 0;
+   LDB_TRY(ldb_read_u64_at(ctx, d_count, &total, site));
+   LdbBufs own(ctx);
+   uint32_t* sel;
+   LDB_TRY(own.alloc(&sel, 4 * (size_t) (total ? total : 1)));
+   if (n_words && total) LDB_TRY(ldb_bitmap_compact(ctx, bitmap, n_words, sel, total, nullptr, nullptr, nullptr));
+   if (done) done->free_all();
+   own.keep(sel);
+   return ldb_rel_select(ctx, src, sel, (int64_t) total, out);
+}
+
+// SEMI_BUILD / ANTI_BUILD: flag the build rows that some probe row matches, then keep (SEMI) / drop (ANTI) them.  With anti_preds (the
+// one-pass semi + anti form, kind = SEMI_BUILD) a second flag per build row marks a partner that also satisfies them, and the rows with the
+// first flag but not the second are kept.
+static int32_t probe_mark_build(ldb_ctx* ctx, ldb_hashtable* ht, ldb_rel* probe, const ldb_colref* keys, int32_t n_keys, int32_t kind, const ldb_join_residual* resid, int32_t n_resid,
+                                const ldb_filter_desc* anti_preds, int32_t n_anti_preds, uint32_t site, ldb_rel** out) {
+   auto hb = std::make_unique<DJoin>();
+   LDB_TRY(make_probe_desc(ht, probe, keys, n_keys, hb.get(), resid, n_resid));
+   hb->kind = kind;
+   for (int32_t p = 0; p < n_anti_preds; p++) LDB_TRY(ldb_make_dpred(probe, &anti_preds[p], &hb->m2preds[p]));
+   hb->n_m2preds = n_anti_preds;
+   const bool two = n_anti_preds > 0;
+   const int64_t nb = ht->build->n_rows, nbw = (nb + 63) / 64;
+   const size_t flag_bytes = (size_t) (nb ? nb : 1);
+   LdbBufs tmp(ctx);
+   uint8_t* flags;
+   uint64_t* bitmap;
+   LDB_TRY(tmp.alloc(&flags, (two ? 2 : 1) * flag_bytes));
+   LDB_TRY(tmp.alloc(&bitmap, 8 * (size_t) (nbw ? nbw : 1)));
+   LDB_HIP(hipMemsetAsync(flags, 0, (two ? 2 : 1) * flag_bytes, ctx->stream));
+   const uint8_t* flags2 = flags + flag_bytes;
+   hb->mark = (uint64_t) flags;
+   if (two) hb->mark2 = (uint64_t) flags2;
+   hb->has_mark = 1;
+   unsigned long long* cnt;
+   LDB_TRY(ldb_counters(ctx, 2, (uint64_t**) &cnt));
+   {
+      LdbDesc<DJoin> d_desc(ctx);
+      LDB_TRY(d_desc.upload(hb.get(), sizeof(DJoin)));
+      if (probe->n_rows) LDB_TRY(launch_join(ctx, hb.get(), d_desc.p, ldb_grid_for(ctx, probe->n_rows, 256, 8), "k_join_probe_markbuild", "k_join_probe_markbuild_spec", k_join_probe_markbuild));
+   }
+   const dim3 fgrid(ldb_grid_for(ctx, nb, 256, 8));
+   if (nb && two) hipLaunchKernelGGL(k_join_flags_bitmap2, fgrid, dim3(256), 0, ctx->stream, (const uint8_t*) flags, flags2, (uint64_t) nb, bitmap, cnt);
+   else if (nb) hipLaunchKernelGGL(k_join_flags_bitmap, fgrid, dim3(256), 0, ctx->stream, (const uint8_t*) flags, (uint64_t) nb, kind == LDB_JOIN_ANTI_BUILD ? 1 : 0, bitmap, cnt);
+   LDB_HIP(hipGetLastError());
+   // (the one-pass form has always kept its flags and bitmap until the selection was composed; SEMI_BUILD / ANTI_BUILD free them first)
+   return select_by_bitmap(ctx, ht->build, bitmap, nbw, cnt, site, two ? nullptr : &tmp, out);
+}
+
 // Build-side semi join AND build-side anti join against the same table in one pass over the probe side: *out = the build rows that have a
 // partner among the probe rows (key equality + residual conjuncts) but NO partner among the probe rows that also satisfy `anti_preds`.
 // Equal to SEMI_BUILD, a table over its result, and ANTI_BUILD probed by `probe` filtered on anti_preds — TPC-H Q21's EXISTS / NOT EXISTS
@@ -1055,94 +1098,233 @@ extern "C" int32_t ldb_gpu_join_probe_semi_anti_build(ldb_ctx* ctx, ldb_hashtabl
    if (!ctx || !ht || !probe || !out || n_keys < 1 || !anti_preds || n_anti_preds < 1) LDB_FAIL(LDB_ERR_INVALID, "join_probe_semi_anti_build: bad argument");
    if (n_anti_preds > LDB_MAX_M2PREDS) LDB_FAIL(LDB_ERR_UNSUPPORTED, "join_probe_semi_anti_build: more than %d conjuncts on the anti side", LDB_MAX_M2PREDS);
    LDB_TRY(ldb_rel_force(ctx, probe)); // (the second marker's conjuncts are evaluated per matching pair; a lazy probe filter is applied first)
-   auto hb = std::make_unique<DJoin>();
-   LDB_TRY(make_probe_desc(ht, probe, keys, n_keys, hb.get(), resid, n_resid));
-   hb->kind = LDB_JOIN_SEMI_BUILD;
-   for (int32_t p = 0; p < n_anti_preds; p++) LDB_TRY(ldb_make_dpred(probe, &anti_preds[p], &hb->m2preds[p]));
-   hb->n_m2preds = n_anti_preds;
-   const int64_t nb = ht->build->n_rows, nbw = (nb + 63) / 64;
-   LdbBufs tmp(ctx);
-   uint8_t *flags, *flags2;
-   uint64_t* bitmap;
-   LDB_TRY(tmp.alloc(&flags, 2 * (size_t) (nb ? nb : 1)));
-   flags2 = flags + (nb ? nb : 1);
-   LDB_TRY(tmp.alloc(&bitmap, 8 * (size_t) (nbw ? nbw : 1)));
-   LDB_HIP(hipMemsetAsync(flags, 0, 2 * (size_t) (nb ? nb : 1), ctx->stream));
-   hb->mark = (uint64_t) flags;
-   hb->mark2 = (uint64_t) flags2;
-   hb->has_mark = 1;
-   unsigned long long* cnt;
-   LDB_TRY(ldb_counters(ctx, 2, (uint64_t**) &cnt));
-   LdbDesc<DJoin> d_desc(ctx);
-   LDB_TRY(d_desc.upload(hb.get(), sizeof(DJoin)));
-   DJoin* d = d_desc.p;
-   int32_t st = LDB_OK;
-   if (probe->n_rows) st = launch_join(ctx, hb.get(), d, ldb_grid_for(ctx, probe->n_rows, 256, 8), "k_join_probe_markbuild", "k_join_probe_markbuild_spec", k_join_probe_markbuild);
-   d_desc.release();
-   LDB_TRY(st);
-   if (nb) hipLaunchKernelGGL(k_join_flags_bitmap2, dim3(ldb_grid_for(ctx, nb, 256, 8)), dim3(256), 0, ctx->stream, (const uint8_t*) flags, (const uint8_t*) flags2, (uint64_t) nb, bitmap, cnt);
-   LDB_HIP(hipGetLastError());
-   uint64_t total = 0;
-   LDB_TRY(ldb_read_u64(ctx, cnt, &total));
-   uint32_t* sel;
-   LDB_TRY(ldb_dev_alloc(ctx, (void**) &sel, 4 * (size_t) (total ? total : 1)));
-   if (nbw && total) {
-      st = ldb_bitmap_compact(ctx, bitmap, nbw, sel, total, nullptr, nullptr, nullptr);
-      if (st != LDB_OK) {
-         ldb_dev_free(ctx, sel);
-         return st;
-      }
-   }
-   return ldb_rel_select(ctx, ht->build, sel, (int64_t) total, out);
+   return probe_mark_build(ctx, ht, probe, keys, n_keys, LDB_JOIN_SEMI_BUILD, resid, n_resid, anti_preds, n_anti_preds, LDB_SITE, out);
 }
 
+// RIGHT / FULL outer: the pairs of the inner / left-outer join, then the build rows whose marker no probe tuple set (the reference
+// scans its HashMultiMap for unmarked entries after the probe pipeline, translateHJWithMarker)
+static int32_t probe_outer(ldb_ctx* ctx, ldb_hashtable* ht, ldb_rel* probe, const ldb_colref* keys, int32_t n_keys, int32_t kind, const ldb_join_residual* resid, int32_t n_resid, ldb_rel** out,
+                           bool radix_ok) {
+   LdbRelHold pairs(ctx), unm(ctx);
+   LDB_TRY(probe_impl(ctx, ht, probe, keys, n_keys, kind == LDB_JOIN_RIGHT_OUTER ? LDB_JOIN_INNER : LDB_JOIN_LEFT_OUTER, resid, n_resid, &pairs.r, nullptr, radix_ok));
+   LDB_TRY(probe_impl(ctx, ht, probe, keys, n_keys, LDB_JOIN_ANTI_BUILD, resid, n_resid, &unm.r, nullptr, radix_ok));
+   const int64_t n1 = pairs->n_rows, n2 = unm->n_rows, nn = n1 + n2;
+   if (nn >= (int64_t) LDB_NULL_ROW) LDB_FAIL(LDB_ERR_UNSUPPORTED, "join_probe: %ld result rows exceed uint32 row ids", (long) nn);
+   const size_t np = probe->sides.size(), nb = ht->build->sides.size();
+   if (pairs->sides.size() != np + nb || unm->sides.size() != nb) LDB_FAIL(LDB_ERR_INVALID, "join_probe: outer join pieces do not line up");
+   LdbRelHold r(ctx, ldb_rel_new(ctx));
+   r->n_rows = nn;
+   const int cg = ldb_grid_for(ctx, nn, 256, 8);
+   for (size_t j = 0; j < np + nb; j++) {
+      const ldb_rel_side& a = pairs->sides[j];
+      const bool may_null = j >= np ? a.may_null || unm->sides[j - np].may_null : true;
+      uint32_t* ids;
+      LDB_TRY(ldb_rel_push_side(r.r, a.table, may_null, (size_t) nn, &ids));
+      const uint32_t* tail = j >= np ? unm->sides[j - np].rowids : nullptr;
+      if (nn) hipLaunchKernelGGL(k_concat_rowids, dim3(cg), dim3(256), 0, ctx->stream, (const uint32_t*) a.rowids, (uint64_t) n1, tail, (uint64_t) n2, j < np ? 1 : 0, ids);
+   }
+   LDB_HIP(hipGetLastError());
+   *out = r.release();
+   return LDB_OK;
+}
+
+// what the exists / unique / pairs probes start from: the probe descriptor (host copy), its counters and the launch geometry
+struct ProbeCall {
+   std::unique_ptr<DJoin> h = std::make_unique<DJoin>();
+   unsigned long long* counter = nullptr; // [0] rows produced, [1] matches (+ 3 debug words): zeroed arena words
+   int64_t n = 0, n_words = 0;
+   int grid = 1;
+};
+
+// SEMI / ANTI / MARK: one bit per probe row
+static int32_t probe_exists(ldb_ctx* ctx, ldb_rel* probe, ProbeCall& pc, int32_t kind, ldb_rel** out, ldb_table** mark_out) {
+   DJoin* h = pc.h.get();
+   const int64_t n = pc.n;
+   LdbBufs tmp(ctx);
+   uint64_t* bitmap;
+   LDB_TRY(tmp.alloc(&bitmap, 8 * (size_t) (pc.n_words ? pc.n_words : 1)));
+   h->bitmap = (uint64_t) bitmap;
+   h->has_bitmap = 1;
+   LdbTableHold mark(ctx);
+   if (kind == LDB_JOIN_MARK) {
+      if (!mark_out) LDB_FAIL(LDB_ERR_INVALID, "join_probe: MARK needs mark_out");
+      ldb_coltype t = {LDB_T_BOOL8, 0, 0, 0};
+      const char* nm = "mark";
+      LDB_TRY(ldb_gpu_table_alloc(ctx, "mark", 1, &t, &nm, n, nullptr, 0, &mark.t));
+      h->mark = (uint64_t) mark->cols[0].values;
+      h->has_mark = 1;
+   }
+   {
+      LdbDesc<DJoin> d_desc(ctx);
+      LDB_TRY(d_desc.upload(h, sizeof(*h)));
+      if (n) LDB_TRY(launch_join(ctx, h, d_desc.p, pc.grid, "k_join_probe_exists", "k_join_probe_exists_spec", k_join_probe_exists));
+   }
+   if (kind != LDB_JOIN_MARK) return select_by_bitmap(ctx, probe, bitmap, pc.n_words, pc.counter, LDB_SITE, &tmp, out);
+   tmp.free(bitmap);
+   // all probe rows in input order
+   LdbRelHold r(ctx, ldb_rel_new(ctx));
+   r->n_rows = n;
+   LDB_TRY(ldb_rel_copy_sides(r.r, probe));
+   *mark_out = mark.release();
+   *out = r.release();
+   return LDB_OK;
+}
+
+// The sides of `src` seen through the selection `sel` (n row numbers; selection `which` of the compose launch) become sides of r.  The first
+// identity side IS the selection: it takes `sel` out of `bufs`, no copy; every other side gets a vector of its own and a compose job.
+static int32_t compose_sides(LdbBufs& bufs, ldb_rel* r, const ldb_rel* src, uint32_t* sel, int which, bool sel_may_null, size_t n, std::vector<LdbComposeJob>& jobs) {
+   bool sel_taken = false;
+   for (auto& s : src->sides) {
+      if (!s.rowids && !sel_taken) {
+         r->sides.push_back(ldb_rel_side{s.table, sel, true, s.may_null || sel_may_null});
+         bufs.keep(sel);
+         sel_taken = true;
+      } else {
+         uint32_t* ids;
+         LDB_TRY(ldb_rel_push_side(r, s.table, s.may_null || sel_may_null, n, &ids));
+         jobs.push_back({(const uint32_t*) s.rowids, ids, which});
+      }
+   }
+   return LDB_OK;
+}
+
+// result relation of a pairs-shaped probe: probe sides composed with op, build sides composed with ob (both in `bufs`)
+static int32_t probe_hand_over(ldb_ctx* ctx, LdbBufs& bufs, ldb_hashtable* ht, ldb_rel* probe, const DJoin* h, int32_t kind, uint32_t* op, uint32_t* ob, uint64_t produced, ldb_rel** out) {
+   if (ldb_option("debug_check", 0)) {
+      LDB_TRY(debug_check_ids(ctx, "probe", op, produced, probe->n_rows, h));
+      LDB_TRY(debug_check_ids(ctx, "build", ob, produced, ht->build->n_rows, h));
+   }
+   LdbRelHold r(ctx, ldb_rel_new(ctx));
+   r->n_rows = (int64_t) produced;
+   // LEFT_OUTER / SINGLE pad the build sides of unmatched probe rows with LDB_NULL_ROW
+   const bool pads = kind == LDB_JOIN_LEFT_OUTER || kind == LDB_JOIN_SINGLE;
+   std::vector<LdbComposeJob> jobs; // every side that needs its own vector: composed in ONE launch below
+   LDB_TRY(compose_sides(bufs, r.r, probe, op, 0, false, (size_t) produced, jobs));
+   LDB_TRY(compose_sides(bufs, r.r, ht->build, ob, 1, pads, (size_t) produced, jobs));
+   LDB_TRY(ldb_compose_rowids(ctx, op, ob, jobs.data(), (int) jobs.size(), produced));
+   *out = r.release();
+   return LDB_OK;
+}
+
+// unique build keys — at most one match per probe row: dense match vector + ordered bitmap compaction
+static int32_t probe_unique(ldb_ctx* ctx, ldb_hashtable* ht, ldb_rel* probe, ProbeCall& pc, int32_t kind, int32_t n_resid, const RadixProbe* part, ldb_rel** out) {
+   DJoin* h = pc.h.get();
+   const int64_t n = pc.n, n_words = pc.n_words;
+   unsigned long long* counter = pc.counter;
+   LdbBufs bufs(ctx);
+   uint32_t* match;
+   uint64_t* bitmap = nullptr;
+   LDB_TRY(bufs.alloc(&match, 4 * (size_t) (n ? n : 1)));
+   if (kind == LDB_JOIN_INNER) {
+      LDB_TRY(bufs.alloc(&bitmap, 8 * (size_t) (n_words ? n_words : 1)));
+      h->has_bitmap = 1;
+   }
+   h->match = (uint64_t) match;
+   h->bitmap = (uint64_t) bitmap;
+   {
+      LdbDesc<DJoin> d_desc(ctx);
+      LDB_TRY(d_desc.upload(h, sizeof(*h)));
+      if (n && part_probe_ok(ht, part, n_resid) && probe->pending.empty()) LDB_TRY(launch_part_probe(ctx, ht, part, n, 1, match, bitmap, counter)); // partitions staged in LDS
+      else if (n) LDB_TRY(launch_join(ctx, h, d_desc.p, pc.grid, "k_join_probe_unique", "k_join_probe_unique_spec", k_join_probe_unique));
+   }
+   if (getenv("LDB_DEBUG_COUNTS")) {
+      uint64_t c[3];
+      for (int k = 0; k < 3; k++) LDB_TRY(ldb_read_u64(ctx, counter + 2 + k, &c[k]));
+      fprintf(stderr, "[debug counts] queued %llu key-bit hits %llu matches %llu\n", (unsigned long long) c[0], (unsigned long long) c[1], (unsigned long long) c[2]);
+   }
+   if (kind != LDB_JOIN_INNER) { // LEFT_OUTER / SINGLE: exactly one output row per probe row
+      uint32_t* op;
+      LDB_TRY(bufs.alloc(&op, 4 * (size_t) (n ? n : 1)));
+      if (n) hipLaunchKernelGGL(k_iota_u32j, dim3(pc.grid), dim3(256), 0, ctx->stream, op, (uint64_t) n);
+      return probe_hand_over(ctx, bufs, ht, probe, h, kind, op, match, (uint64_t) n, out);
+   }
+   uint64_t produced = 0;
+   LDB_TRY(ldb_read_u64(ctx, counter, &produced));
+   if (produced == (uint64_t) n && n > 0 && ldb_option("join_all_match", 1) != 0) {
+      // EVERY probe row found its partner (a foreign key probing its primary key: most joins of a TPC-H plan): the result has the probe
+      // relation's rows in the probe relation's order, so its sides carry over as they are — shared, not copied — and match[] IS the
+      // build side's selection.  No bitmap compaction, no composition of the probe sides (round 6; the reference never materialises
+      // between the operators of a pipeline either, SubOpToControlFlow.cpp:1123-1202)
+      if (ctx->trace_mode == 2 && n_words) // a replayed count: should a row be partner-less after all, its match[] word must not be garbage
+         hipLaunchKernelGGL(k_unmatched_to_zero, dim3(ldb_grid_for(ctx, (int64_t) n_words, 256, 8)), dim3(256), 0, ctx->stream, (const uint64_t*) bitmap, match, (uint64_t) n);
+      bufs.free(bitmap);
+      LdbRelHold r(ctx, ldb_rel_new(ctx));
+      r->n_rows = n;
+      for (auto& s : probe->sides) {
+         if (s.rowids) ldb_dev_share(ctx, s.rowids);
+         r->sides.push_back(ldb_rel_side{s.table, s.rowids, s.rowids != nullptr, s.may_null});
+      }
+      std::vector<LdbComposeJob> bjobs;
+      LDB_TRY(compose_sides(bufs, r.r, ht->build, match, 1, false, (size_t) n, bjobs));
+      LDB_TRY(ldb_compose_rowids(ctx, match, match, bjobs.data(), (int) bjobs.size(), (uint64_t) n));
+      *out = r.release();
+      return LDB_OK;
+   }
+   uint32_t *op, *ob;
+   LDB_TRY(bufs.alloc(&op, 4 * (size_t) (produced ? produced : 1)));
+   LDB_TRY(bufs.alloc(&ob, 4 * (size_t) (produced ? produced : 1)));
+   // matched probe rows in ascending order + the build row of each, in one launch
+   if (n_words && produced) LDB_TRY(ldb_bitmap_compact(ctx, bitmap, n_words, op, produced, match, ob, nullptr));
+   bufs.free(bitmap);
+   bufs.free(match);
+   return probe_hand_over(ctx, bufs, ht, probe, h, kind, op, ob, produced, out);
+}
+
+// duplicated build keys: count per 64-row chunk → scan → emit (see join_probe_pairs_body)
+static int32_t probe_pairs(ldb_ctx* ctx, ldb_hashtable* ht, ldb_rel* probe, ProbeCall& pc, int32_t kind, ldb_rel** out) {
+   DJoin* h = pc.h.get();
+   const int64_t n = pc.n, n_chunks = (n + 63) / 64;
+   LdbBufs bufs(ctx);
+   uint32_t *chunk_cnt, *chunk_off, *op, *ob;
+   LDB_TRY(bufs.alloc(&chunk_cnt, 4 * (size_t) (n_chunks ? n_chunks : 1)));
+   LDB_TRY(bufs.alloc(&chunk_off, 4 * (size_t) (n_chunks ? n_chunks : 1)));
+   h->match = (uint64_t) chunk_cnt;
+   uint64_t produced = 0;
+   LdbDesc<DJoin> d_desc(ctx);
+   LDB_TRY(d_desc.upload(h, sizeof(*h)));
+   if (n) {
+      LDB_TRY(launch_join(ctx, h, d_desc.p, pc.grid, "k_join_probe_pairs_count", "k_join_probe_pairs_count_spec", k_join_probe_pairs_count));
+      LDB_TRY(ldb_exclusive_scan_u32(ctx, chunk_cnt, chunk_off, n_chunks, nullptr));
+      LDB_TRY(ldb_read_u64(ctx, pc.counter, &produced));
+   }
+   d_desc.release();
+   if (produced >= (uint64_t) LDB_NULL_ROW) LDB_FAIL(LDB_ERR_UNSUPPORTED, "join_probe: %llu result rows exceed uint32 row ids", (unsigned long long) produced);
+   LDB_TRY(bufs.alloc(&op, 4 * (size_t) (produced ? produced : 1)));
+   LDB_TRY(bufs.alloc(&ob, 4 * (size_t) (produced ? produced : 1)));
+   if (produced) {
+      if (ctx->trace_mode == 2) { // a replayed `produced` may exceed what the kernel really emits: no uninitialised row id behind the real tail
+         LDB_HIP(hipMemsetAsync(op, 0, 4 * (size_t) produced, ctx->stream));
+         LDB_HIP(hipMemsetAsync(ob, 0, 4 * (size_t) produced, ctx->stream));
+      }
+      h->match = (uint64_t) chunk_off;
+      h->out_probe = (uint64_t) op;
+      h->out_build = (uint64_t) ob;
+      h->out_cap = produced;
+      LDB_TRY(d_desc.upload(h, sizeof(*h)));
+      LDB_TRY(launch_join(ctx, h, d_desc.p, pc.grid, "k_join_probe_pairs", "k_join_probe_pairs_spec", k_join_probe_pairs));
+      d_desc.release();
+   }
+   bufs.free(chunk_cnt);
+   bufs.free(chunk_off);
+   return probe_hand_over(ctx, bufs, ht, probe, h, kind, op, ob, produced, out);
+}
+
+// every join kind: checks the arguments, clusters the probe side where that pays, then hands over to the probe of the result's shape
 static int32_t probe_impl(ldb_ctx* ctx, ldb_hashtable* ht, ldb_rel* probe, const ldb_colref* keys, int32_t n_keys, int32_t kind, const ldb_join_residual* resid, int32_t n_resid,
                           ldb_rel** out, ldb_table** mark_out, bool radix_ok, const RadixProbe* part) {
    if (!ctx || !ht || !probe || !out) LDB_FAIL(LDB_ERR_INVALID, "join_probe: NULL argument");
    if (kind < LDB_JOIN_INNER || kind > LDB_JOIN_FULL_OUTER) LDB_FAIL(LDB_ERR_INVALID, "join_probe: bad kind %d", kind);
-   if (kind == LDB_JOIN_RIGHT_OUTER || kind == LDB_JOIN_FULL_OUTER) {
-      // the pairs of the inner / left-outer join, then the build rows whose marker no probe tuple set (the reference
-      // scans its HashMultiMap for unmarked entries after the probe pipeline, translateHJWithMarker)
-      struct RelHold {
-         ldb_ctx* ctx;
-         ldb_rel* r = nullptr;
-         ~RelHold() {
-            if (r) ldb_gpu_rel_release(ctx, r);
-         }
-      } pairs{ctx}, unm{ctx};
-      LDB_TRY(probe_impl(ctx, ht, probe, keys, n_keys, kind == LDB_JOIN_RIGHT_OUTER ? LDB_JOIN_INNER : LDB_JOIN_LEFT_OUTER, resid, n_resid, &pairs.r, nullptr, radix_ok));
-      LDB_TRY(probe_impl(ctx, ht, probe, keys, n_keys, LDB_JOIN_ANTI_BUILD, resid, n_resid, &unm.r, nullptr, radix_ok));
-      const int64_t n1 = pairs.r->n_rows, n2 = unm.r->n_rows, nn = n1 + n2;
-      if (nn >= (int64_t) LDB_NULL_ROW) LDB_FAIL(LDB_ERR_UNSUPPORTED, "join_probe: %ld result rows exceed uint32 row ids", (long) nn);
-      const size_t np = probe->sides.size(), nb = ht->build->sides.size();
-      if (pairs.r->sides.size() != np + nb || unm.r->sides.size() != nb) LDB_FAIL(LDB_ERR_INVALID, "join_probe: outer join pieces do not line up");
-      ldb_rel* r = ldb_rel_new(ctx);
-      r->n_rows = nn;
-      const int cg = ldb_grid_for(ctx, nn, 256, 8);
-      for (size_t j = 0; j < np + nb; j++) {
-         const ldb_rel_side& a = pairs.r->sides[j];
-         ldb_rel_side ns{a.table, nullptr, true, true};
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &ns.rowids, 4 * (size_t) (nn ? nn : 1)));
-         const uint32_t* tail = j >= np ? unm.r->sides[j - np].rowids : nullptr;
-         if (nn) hipLaunchKernelGGL(k_concat_rowids, dim3(cg), dim3(256), 0, ctx->stream, (const uint32_t*) a.rowids, (uint64_t) n1, tail, (uint64_t) n2, j < np ? 1 : 0, ns.rowids);
-         if (j >= np) ns.may_null = a.may_null || unm.r->sides[j - np].may_null;
-         r->sides.push_back(ns);
-      }
-      LDB_HIP(hipGetLastError());
-      *out = r;
-      return LDB_OK;
-   }
+   if (kind == LDB_JOIN_RIGHT_OUTER || kind == LDB_JOIN_FULL_OUTER) return probe_outer(ctx, ht, probe, keys, n_keys, kind, resid, n_resid, out, radix_ok);
    if (radix_ok) {
-      RadixProbe rp;
+      RadixProbe rp(ctx);
       LDB_TRY(radix_prepare(ctx, ht, probe, keys, n_keys, kind, rp));
       if (rp.rel) { // an unclustered probe side: partitioned by slot range first, then the ordinary kernels
          const ldb_colref k0 = {0, 0};
          std::vector<ldb_join_residual> rs(resid, resid + (n_resid > 0 ? n_resid : 0));
          for (auto& x : rs) x.probe_col.side += 1; // the key table sits in front of the probe's sides
-         const int32_t st = probe_impl(ctx, ht, rp.rel, &k0, 1, kind, rs.data(), n_resid, out, mark_out, false, &rp);
-         if (st == LDB_OK && kind != LDB_JOIN_SEMI_BUILD && kind != LDB_JOIN_ANTI_BUILD) radix_strip(ctx, *out);
-         radix_release(ctx, rp);
-         return st;
+         LDB_TRY(probe_impl(ctx, ht, rp.rel, &k0, 1, kind, rs.data(), n_resid, out, mark_out, false, &rp));
+         if (kind != LDB_JOIN_SEMI_BUILD && kind != LDB_JOIN_ANTI_BUILD) radix_strip(ctx, *out);
+         return LDB_OK;
       }
    }
    // kinds that emit a row for EVERY probe row (outer / single / mark) need the filtered row set itself
@@ -1151,240 +1333,21 @@ static int32_t probe_impl(ldb_ctx* ctx, ldb_hashtable* ht, ldb_rel* probe, const
    // front of a queue that then holds almost nothing — Q12's five conjuncts keep 0.5 % of lineitem: 3.5 ms fused, 2.3 ms as a scan + a probe of the
    // 3 M survivors.  Up to three conjuncts (every other filtered probe of the 22 plans: one or two) stay fused
    if ((int64_t) probe->pending.size() > ldb_option("join_fuse_max_conjuncts", 3)) LDB_TRY(ldb_rel_force(ctx, probe));
+   if (kind == LDB_JOIN_SEMI_BUILD || kind == LDB_JOIN_ANTI_BUILD) return probe_mark_build(ctx, ht, probe, keys, n_keys, kind, resid, n_resid, nullptr, 0, LDB_SITE, out);
    const bool pairs = kind == LDB_JOIN_INNER || kind == LDB_JOIN_LEFT_OUTER || kind == LDB_JOIN_SINGLE;
-   if (kind == LDB_JOIN_SEMI_BUILD || kind == LDB_JOIN_ANTI_BUILD) {
-      // flag the build rows that some probe row matches, then keep (SEMI) / drop (ANTI) them
-      auto hb = std::make_unique<DJoin>();
-      LDB_TRY(make_probe_desc(ht, probe, keys, n_keys, hb.get(), resid, n_resid));
-      hb->kind = kind;
-      const int64_t nb = ht->build->n_rows, nbw = (nb + 63) / 64;
-      uint8_t* flags;
-      uint64_t* bitmap;
-      LDB_TRY(ldb_dev_alloc(ctx, (void**) &flags, (size_t) (nb ? nb : 1)));
-      LDB_TRY(ldb_dev_alloc(ctx, (void**) &bitmap, 8 * (size_t) (nbw ? nbw : 1)));
-      LDB_HIP(hipMemsetAsync(flags, 0, (size_t) (nb ? nb : 1), ctx->stream));
-      hb->mark = (uint64_t) flags;
-      hb->has_mark = 1;
-      unsigned long long* cnt;
-      LDB_TRY(ldb_counters(ctx, 2, (uint64_t**) &cnt));
-      LdbDesc<DJoin> d_desc(ctx);
-      LDB_TRY(d_desc.upload(hb.get(), sizeof(DJoin)));
-      DJoin* d = d_desc.p;
-      if (probe->n_rows) LDB_TRY(launch_join(ctx, hb.get(), d, ldb_grid_for(ctx, probe->n_rows, 256, 8), "k_join_probe_markbuild", "k_join_probe_markbuild_spec", k_join_probe_markbuild));
-      d_desc.release();
-      if (nb) hipLaunchKernelGGL(k_join_flags_bitmap, dim3(ldb_grid_for(ctx, nb, 256, 8)), dim3(256), 0, ctx->stream, (const uint8_t*) flags, (uint64_t) nb, kind == LDB_JOIN_ANTI_BUILD ? 1 : 0, bitmap, cnt);
-      LDB_HIP(hipGetLastError());
-      uint64_t total = 0;
-      LDB_TRY(ldb_read_u64(ctx, cnt, &total));
-      uint32_t* sel;
-      LDB_TRY(ldb_dev_alloc(ctx, (void**) &sel, 4 * (size_t) (total ? total : 1)));
-      if (nbw && total) LDB_TRY(ldb_bitmap_compact(ctx, bitmap, nbw, sel, total, nullptr, nullptr, nullptr));
-      ldb_dev_free(ctx, flags);
-      ldb_dev_free(ctx, bitmap);
-      return ldb_rel_select(ctx, ht->build, sel, (int64_t) total, out);
-   }
    if (pairs && probe->sides.size() + ht->build->sides.size() > LDB_MAX_SIDES)
       LDB_FAIL(LDB_ERR_UNSUPPORTED, "join_probe: result would have more than %d sides (materialize first)", LDB_MAX_SIDES);
-   auto hp = std::make_unique<DJoin>();
-   DJoin* h = hp.get();
-   LDB_TRY(make_probe_desc(ht, probe, keys, n_keys, h, resid, n_resid));
-   h->kind = kind;
-   unsigned long long* counter; // [0] rows produced, [1] matches (+ 3 debug words): zeroed arena words
-   LDB_TRY(ldb_counters(ctx, 6, (uint64_t**) &counter));
-   h->counter = (uint64_t) counter;
-   const int64_t n = probe->n_rows;
-   const int64_t n_words = (n + 63) / 64;
-   const int grid = ldb_grid_for(ctx, n, 256, 8);
-
-   if (!pairs) { // SEMI / ANTI / MARK
-      uint64_t* bitmap;
-      LDB_TRY(ldb_dev_alloc(ctx, (void**) &bitmap, 8 * (size_t) (n_words ? n_words : 1)));
-      h->bitmap = (uint64_t) bitmap;
-      h->has_bitmap = 1;
-      ldb_table* mark = nullptr;
-      if (kind == LDB_JOIN_MARK) {
-         if (!mark_out) LDB_FAIL(LDB_ERR_INVALID, "join_probe: MARK needs mark_out");
-         ldb_coltype t = {LDB_T_BOOL8, 0, 0, 0};
-         const char* nm = "mark";
-         LDB_TRY(ldb_gpu_table_alloc(ctx, "mark", 1, &t, &nm, n, nullptr, 0, &mark));
-         h->mark = (uint64_t) mark->cols[0].values;
-         h->has_mark = 1;
-      }
-      LdbDesc<DJoin> d_desc(ctx);
-      LDB_TRY(d_desc.upload(h, sizeof(*h)));
-      DJoin* d = d_desc.p;
-      if (n) LDB_TRY(launch_join(ctx, h, d, grid, "k_join_probe_exists", "k_join_probe_exists_spec", k_join_probe_exists));
-      d_desc.release();
-      if (kind == LDB_JOIN_MARK) {
-         ldb_dev_free(ctx, bitmap);
-         *mark_out = mark;
-         // all probe rows in input order
-         ldb_rel* r = ldb_rel_new(ctx);
-         r->n_rows = n;
-         for (auto& s : probe->sides) {
-            ldb_rel_side ns{s.table, nullptr, false, s.may_null};
-            if (s.rowids) {
-               LDB_TRY(ldb_dev_alloc(ctx, (void**) &ns.rowids, 4 * (size_t) (n ? n : 1)));
-               if (n) LDB_HIP(hipMemcpyAsync(ns.rowids, s.rowids, 4 * (size_t) n, hipMemcpyDeviceToDevice, ctx->stream));
-               ns.owned = true;
-            }
-            r->sides.push_back(ns);
-         }
-         *out = r;
-         return LDB_OK;
-      }
-      uint64_t total = 0;
-      LDB_TRY(ldb_read_u64(ctx, counter, &total));
-      uint32_t* sel;
-      LDB_TRY(ldb_dev_alloc(ctx, (void**) &sel, 4 * (size_t) (total ? total : 1)));
-      if (n_words && total) LDB_TRY(ldb_bitmap_compact(ctx, bitmap, n_words, sel, total, nullptr, nullptr, nullptr));
-      ldb_dev_free(ctx, bitmap);
-      return ldb_rel_select(ctx, probe, sel, (int64_t) total, out);
-   }
-
-   uint32_t *op = nullptr, *ob = nullptr;
-   uint64_t produced = 0;
-   if (ht->unique) {
-      // at most one match per probe row: dense match vector + ordered bitmap compaction
-      uint32_t* match;
-      uint64_t* bitmap = nullptr;
-      LDB_TRY(ldb_dev_alloc(ctx, (void**) &match, 4 * (size_t) (n ? n : 1)));
-      if (kind == LDB_JOIN_INNER) {
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &bitmap, 8 * (size_t) (n_words ? n_words : 1)));
-         h->has_bitmap = 1;
-      }
-      h->match = (uint64_t) match;
-      h->bitmap = (uint64_t) bitmap;
-      LdbDesc<DJoin> d_desc(ctx);
-      LDB_TRY(d_desc.upload(h, sizeof(*h)));
-      DJoin* d = d_desc.p;
-      if (n && part_probe_ok(ht, part, n_resid) && probe->pending.empty()) LDB_TRY(launch_part_probe(ctx, ht, part, n, 1, match, bitmap, counter)); // partitions staged in LDS
-      else if (n) LDB_TRY(launch_join(ctx, h, d, grid, "k_join_probe_unique", "k_join_probe_unique_spec", k_join_probe_unique));
-      d_desc.release();
-      if (getenv("LDB_DEBUG_COUNTS")) {
-         uint64_t c[3];
-         for (int k = 0; k < 3; k++) LDB_TRY(ldb_read_u64(ctx, counter + 2 + k, &c[k]));
-         fprintf(stderr, "[debug counts] queued %llu key-bit hits %llu matches %llu\n", (unsigned long long) c[0], (unsigned long long) c[1], (unsigned long long) c[2]);
-      }
-      if (kind == LDB_JOIN_INNER) {
-         LDB_TRY(ldb_read_u64(ctx, counter, &produced));
-         if (produced == (uint64_t) n && n > 0 && ldb_option("join_all_match", 1) != 0) {
-            // EVERY probe row found its partner (a foreign key probing its primary key: most joins of a TPC-H plan): the result has the probe
-            // relation's rows in the probe relation's order, so its sides carry over as they are — shared, not copied — and match[] IS the
-            // build side's selection.  No bitmap compaction, no composition of the probe sides (round 6; the reference never materialises
-            // between the operators of a pipeline either, SubOpToControlFlow.cpp:1123-1202)
-            if (ctx->trace_mode == 2 && n_words) // a replayed count: should a row be partner-less after all, its match[] word must not be garbage
-               hipLaunchKernelGGL(k_unmatched_to_zero, dim3(ldb_grid_for(ctx, (int64_t) n_words, 256, 8)), dim3(256), 0, ctx->stream, (const uint64_t*) bitmap, match, (uint64_t) n);
-            ldb_dev_free(ctx, bitmap);
-            ldb_rel* r = ldb_rel_new(ctx);
-            r->n_rows = n;
-            for (auto& s : probe->sides) {
-               ldb_rel_side ns{s.table, s.rowids, s.rowids != nullptr, s.may_null};
-               if (s.rowids) ldb_dev_share(ctx, s.rowids);
-               r->sides.push_back(ns);
-            }
-            std::vector<LdbComposeJob> bjobs;
-            bool match_taken = false;
-            for (auto& s : ht->build->sides) {
-               ldb_rel_side ns{s.table, nullptr, true, s.may_null};
-               if (!s.rowids && !match_taken) {
-                  ns.rowids = match;
-                  match_taken = true;
-               } else {
-                  LDB_TRY(ldb_dev_alloc(ctx, (void**) &ns.rowids, 4 * (size_t) n));
-                  bjobs.push_back({(const uint32_t*) s.rowids, ns.rowids, 1});
-               }
-               r->sides.push_back(ns);
-            }
-            LDB_TRY(ldb_compose_rowids(ctx, match, match, bjobs.data(), (int) bjobs.size(), (uint64_t) n));
-            if (!match_taken) ldb_dev_free(ctx, match);
-            *out = r;
-            return LDB_OK;
-         }
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &op, 4 * (size_t) (produced ? produced : 1)));
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &ob, 4 * (size_t) (produced ? produced : 1)));
-         // matched probe rows in ascending order + the build row of each, in one launch
-         if (n_words && produced) LDB_TRY(ldb_bitmap_compact(ctx, bitmap, n_words, op, produced, match, ob, nullptr));
-         ldb_dev_free(ctx, bitmap);
-         ldb_dev_free(ctx, match);
-      } else { // LEFT_OUTER / SINGLE: exactly one output row per probe row
-         produced = (uint64_t) n;
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &op, 4 * (size_t) (n ? n : 1)));
-         if (n) hipLaunchKernelGGL(k_iota_u32j, dim3(grid), dim3(256), 0, ctx->stream, op, (uint64_t) n);
-         ob = match;
-      }
-   } else {
-      // duplicated build keys: count per 64-row chunk → scan → emit (see join_probe_pairs_body)
-      const int64_t n_chunks = (n + 63) / 64;
-      uint32_t *chunk_cnt, *chunk_off;
-      LDB_TRY(ldb_dev_alloc(ctx, (void**) &chunk_cnt, 4 * (size_t) (n_chunks ? n_chunks : 1)));
-      LDB_TRY(ldb_dev_alloc(ctx, (void**) &chunk_off, 4 * (size_t) (n_chunks ? n_chunks : 1)));
-      h->match = (uint64_t) chunk_cnt;
-      LdbDesc<DJoin> d_desc(ctx);
-      LDB_TRY(d_desc.upload(h, sizeof(*h)));
-      DJoin* d = d_desc.p;
-      if (n) {
-         LDB_TRY(launch_join(ctx, h, d, grid, "k_join_probe_pairs_count", "k_join_probe_pairs_count_spec", k_join_probe_pairs_count));
-         LDB_TRY(ldb_exclusive_scan_u32(ctx, chunk_cnt, chunk_off, n_chunks, nullptr));
-         LDB_TRY(ldb_read_u64(ctx, counter, &produced));
-      }
-      d_desc.release();
-      if (produced >= (uint64_t) LDB_NULL_ROW) LDB_FAIL(LDB_ERR_UNSUPPORTED, "join_probe: %llu result rows exceed uint32 row ids", (unsigned long long) produced);
-      LDB_TRY(ldb_dev_alloc(ctx, (void**) &op, 4 * (size_t) (produced ? produced : 1)));
-      LDB_TRY(ldb_dev_alloc(ctx, (void**) &ob, 4 * (size_t) (produced ? produced : 1)));
-      if (produced) {
-         if (ctx->trace_mode == 2) { // a replayed `produced` may exceed what the kernel really emits: no uninitialised row id behind the real tail
-            LDB_HIP(hipMemsetAsync(op, 0, 4 * (size_t) produced, ctx->stream));
-            LDB_HIP(hipMemsetAsync(ob, 0, 4 * (size_t) produced, ctx->stream));
-         }
-         h->match = (uint64_t) chunk_off;
-         h->out_probe = (uint64_t) op;
-         h->out_build = (uint64_t) ob;
-         h->out_cap = produced;
-         LDB_TRY(d_desc.upload(h, sizeof(*h)));
-         d = d_desc.p;
-         LDB_TRY(launch_join(ctx, h, d, grid, "k_join_probe_pairs", "k_join_probe_pairs_spec", k_join_probe_pairs));
-         d_desc.release();
-      }
-      ldb_dev_free(ctx, chunk_cnt);
-      ldb_dev_free(ctx, chunk_off);
-   }
-   if (ldb_option("debug_check", 0)) {
-      LDB_TRY(debug_check_ids(ctx, "probe", op, produced, probe->n_rows, h));
-      LDB_TRY(debug_check_ids(ctx, "build", ob, produced, ht->build->n_rows, h));
-   }
-   // result relation: probe sides composed with op, build sides composed with ob
-   ldb_rel* r = ldb_rel_new(ctx);
-   r->n_rows = (int64_t) produced;
-   const int cg = ldb_grid_for(ctx, (int64_t) produced, 256, 8);
-   // LEFT_OUTER / SINGLE pad the build sides of unmatched probe rows with LDB_NULL_ROW
-   const bool pads = kind == LDB_JOIN_LEFT_OUTER || kind == LDB_JOIN_SINGLE;
-   std::vector<LdbComposeJob> jobs; // every side that needs its own vector: composed in ONE launch below
-   bool free_op = false, free_ob = false;
-   auto add_sides = [&](ldb_rel* src, uint32_t* sel, int which, bool sel_may_null, bool* free_sel) -> int32_t {
-      bool sel_taken = false; // the first identity side IS the selection vector: hand it over, no copy
-      for (auto& s : src->sides) {
-         ldb_rel_side ns{s.table, nullptr, true, s.may_null || sel_may_null};
-         if (!s.rowids && !sel_taken) {
-            ns.rowids = sel;
-            sel_taken = true;
-         } else {
-            LDB_TRY(ldb_dev_alloc(ctx, (void**) &ns.rowids, 4 * (size_t) (produced ? produced : 1)));
-            jobs.push_back({(const uint32_t*) s.rowids, ns.rowids, which});
-         }
-         r->sides.push_back(ns);
-      }
-      *free_sel = !sel_taken;
-      return LDB_OK;
-   };
-   (void) cg;
-   LDB_TRY(add_sides(probe, op, 0, false, &free_op));
-   LDB_TRY(add_sides(ht->build, ob, 1, pads, &free_ob));
-   LDB_TRY(ldb_compose_rowids(ctx, op, ob, jobs.data(), (int) jobs.size(), produced));
-   if (free_op) ldb_dev_free(ctx, op);
-   if (free_ob) ldb_dev_free(ctx, ob);
-   *out = r;
-   return LDB_OK;
+   ProbeCall pc;
+   LDB_TRY(make_probe_desc(ht, probe, keys, n_keys, pc.h.get(), resid, n_resid));
+   pc.h->kind = kind;
+   LDB_TRY(ldb_counters(ctx, 6, (uint64_t**) &pc.counter));
+   pc.h->counter = (uint64_t) pc.counter;
+   pc.n = probe->n_rows;
+   pc.n_words = (pc.n + 63) / 64;
+   pc.grid = ldb_grid_for(ctx, pc.n, 256, 8);
+   if (!pairs) return probe_exists(ctx, probe, pc, kind, out, mark_out);
+   if (ht->unique) return probe_unique(ctx, ht, probe, pc, kind, n_resid, part, out);
+   return probe_pairs(ctx, ht, probe, pc, kind, out);
 }
 
 // ---------------------------------------------------------------- nested-loop join
@@ -1397,7 +1360,7 @@ static int32_t probe_impl(ldb_ctx* ctx, ldb_hashtable* ht, ldb_rel* probe, const
 static void strip_table_sides(ldb_ctx* ctx, ldb_rel* r, const ldb_table* t) {
    for (size_t k = 0; k < r->sides.size();) {
       if (r->sides[k].table == t) {
-         if (r->sides[k].owned) ldb_dev_free(ctx, r->sides[k].rowids);
+         if (r->sides[k].owned) LdbBufs::drop(ctx, &r->sides[k].rowids);
          r->sides.erase(r->sides.begin() + (long) k);
       } else {
          k++;

@@ -136,30 +136,27 @@ static int32_t build_scan_desc(ldb_rel* in, const ldb_filter_desc* preds, int32_
 }
 
 // Restrict relation `in` to the logical rows listed in `sel` (device, n_sel entries, ascending).
-// Takes ownership of `sel`.
+// Takes ownership of `sel`, on error returns too.
 int32_t ldb_rel_select(ldb_ctx* ctx, ldb_rel* in, uint32_t* sel, int64_t n_sel, ldb_rel** out) {
-   ldb_rel* r = ldb_rel_new(ctx);
+   LdbBufs own(ctx);
+   own.adopt(sel);
+   LdbRelHold r(ctx, ldb_rel_new(ctx));
    r->n_rows = n_sel;
    bool sel_used = false;
    std::vector<LdbComposeJob> jobs; // all sides that need a vector of their own: one launch
    for (auto& s : in->sides) {
-      ldb_rel_side ns;
-      ns.table = s.table;
-      ns.may_null = s.may_null;
       if (!s.rowids && !sel_used) {
-         ns.rowids = sel;
-         ns.owned = true;
+         r->sides.push_back(ldb_rel_side{s.table, sel, true, s.may_null});
+         own.keep(sel);
          sel_used = true;
       } else { // (a second identity side over the same logical rows gets a copy of the selection: ids == NULL)
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &ns.rowids, sizeof(uint32_t) * (size_t) (n_sel ? n_sel : 1)));
-         ns.owned = true;
-         jobs.push_back({(const uint32_t*) s.rowids, ns.rowids, 0});
+         uint32_t* ids;
+         LDB_TRY(ldb_rel_push_side(r.r, s.table, s.may_null, (size_t) n_sel, &ids));
+         jobs.push_back({(const uint32_t*) s.rowids, ids, 0});
       }
-      r->sides.push_back(ns);
    }
    LDB_TRY(ldb_compose_rowids(ctx, sel, nullptr, jobs.data(), (int) jobs.size(), (uint64_t) n_sel));
-   if (!sel_used) ldb_dev_free(ctx, sel);
-   *out = r;
+   *out = r.release();
    return LDB_OK;
 }
 
@@ -169,9 +166,11 @@ template <typename LAUNCH>
 static int32_t scan_run_with(ldb_ctx* ctx, int64_t n, LAUNCH launch, uint32_t** sel_out, uint64_t* total_out) {
    const int64_t n_words = (n + 63) / 64;
    const int64_t n_blocks = (n_words + SCAN_WORDS_PER_BLOCK - 1) / SCAN_WORDS_PER_BLOCK;
+   LdbBufs tmp(ctx);
    uint32_t* sel;
    if (n == 0) {
-      LDB_TRY(ldb_dev_alloc(ctx, (void**) &sel, 16));
+      LDB_TRY(tmp.alloc(&sel, 16));
+      tmp.keep(sel);
       *sel_out = sel;
       *total_out = 0;
       return LDB_OK;
@@ -182,9 +181,9 @@ static int32_t scan_run_with(ldb_ctx* ctx, int64_t n, LAUNCH launch, uint32_t** 
       while (parts < 16 && n_blocks * parts < 2048) parts *= 2;
    uint64_t* bitmap;
    uint32_t *counts, *offsets;
-   LDB_TRY(ldb_dev_alloc(ctx, (void**) &bitmap, sizeof(uint64_t) * (size_t) n_words));
-   LDB_TRY(ldb_dev_alloc(ctx, (void**) &counts, sizeof(uint32_t) * (size_t) n_blocks * parts));
-   LDB_TRY(ldb_dev_alloc(ctx, (void**) &offsets, sizeof(uint32_t) * (size_t) n_blocks * parts));
+   LDB_TRY(tmp.alloc(&bitmap, sizeof(uint64_t) * (size_t) n_words));
+   LDB_TRY(tmp.alloc(&counts, sizeof(uint32_t) * (size_t) n_blocks * parts));
+   LDB_TRY(tmp.alloc(&offsets, sizeof(uint32_t) * (size_t) n_blocks * parts));
    LDB_TRY(launch(bitmap, counts, (unsigned) n_blocks, parts));
    LDB_HIP(hipGetLastError());
    uint64_t* d_total;
@@ -196,12 +195,10 @@ static int32_t scan_run_with(ldb_ctx* ctx, int64_t n, LAUNCH launch, uint32_t** 
    // see that the execution took another path, check what it replayed and record from there, instead of replaying a wrong count and losing
    // the whole execution at the final comparison: 7 of the 22 queries paid that once during warm-up)
    LDB_TRY(ldb_read_u64_at(ctx, d_total, &total, ldb_site_derived(LDB_SITE, (uint32_t) n), 0));
-   LDB_TRY(ldb_dev_alloc(ctx, (void**) &sel, sizeof(uint32_t) * (size_t) (total ? total : 1)));
+   LDB_TRY(tmp.alloc(&sel, sizeof(uint32_t) * (size_t) (total ? total : 1)));
    if (total) hipLaunchKernelGGL(k_scan_expand, dim3((unsigned) n_blocks), dim3(SCAN_BLOCK), 0, ctx->stream, bitmap, offsets, sel, (uint64_t) n, total, (uint32_t) parts);
    LDB_HIP(hipGetLastError());
-   ldb_dev_free(ctx, bitmap);
-   ldb_dev_free(ctx, counts);
-   ldb_dev_free(ctx, offsets);
+   tmp.keep(sel);
    *sel_out = sel;
    *total_out = total;
    return LDB_OK;
@@ -316,11 +313,10 @@ int32_t ldb_rel_force(ldb_ctx* ctx, ldb_rel* r) {
    uint64_t total;
    LDB_TRY(scan_run(ctx, r, h, &sel, &total));
    r->pending.clear();
-   ldb_rel* m = nullptr;
-   LDB_TRY(ldb_rel_select(ctx, r, sel, (int64_t) total, &m));
+   LdbRelHold m(ctx);
+   LDB_TRY(ldb_rel_select(ctx, r, sel, (int64_t) total, &m.r));
    r->n_rows = m->n_rows;
    r->sides.swap(m->sides); // r was dense: m's old sides (after the swap) own nothing
-   ldb_gpu_rel_release(ctx, m);
    return LDB_OK;
 }
 

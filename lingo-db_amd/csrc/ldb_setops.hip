@@ -27,50 +27,6 @@
 
 int32_t ldb_rel_select(ldb_ctx* ctx, ldb_rel* in, uint32_t* sel, int64_t n_sel, ldb_rel** out);
 
-namespace {
-struct TableGuard {
-   ldb_ctx* ctx;
-   ldb_table* t = nullptr;
-   explicit TableGuard(ldb_ctx* c) : ctx(c) {}
-   ~TableGuard() {
-      if (t) ldb_gpu_table_release(ctx, t);
-   }
-   ldb_table* release() {
-      ldb_table* r = t;
-      t = nullptr;
-      return r;
-   }
-};
-struct RelGuard {
-   ldb_ctx* ctx;
-   ldb_rel* r = nullptr;
-   explicit RelGuard(ldb_ctx* c) : ctx(c) {}
-   ~RelGuard() {
-      if (r) ldb_gpu_rel_release(ctx, r);
-   }
-};
-struct Bufs {
-   ldb_ctx* ctx;
-   std::vector<void*> ptrs;
-   explicit Bufs(ldb_ctx* c) : ctx(c) {}
-   ~Bufs() {
-      for (void* p : ptrs) ldb_dev_free(ctx, p);
-   }
-   template <typename T>
-   int32_t alloc(T** out, size_t bytes) {
-      void* p = nullptr;
-      LDB_TRY(ldb_dev_alloc(ctx, &p, bytes ? bytes : 8));
-      ptrs.push_back(p);
-      *out = (T*) p;
-      return LDB_OK;
-   }
-   void forget(void* p) { // ownership moved elsewhere
-      for (auto& q : ptrs)
-         if (q == p) q = nullptr;
-   }
-};
-} // namespace
-
 // ================================================================== concatenation of two tables (same schema)
 __global__ void k_concat_offsets(const int64_t* __restrict__ a, uint64_t na, const int64_t* __restrict__ b, uint64_t nb, int64_t* __restrict__ out) {
    const uint64_t n = na + nb;
@@ -122,7 +78,7 @@ static int32_t table_concat(ldb_ctx* ctx, const ldb_table* a, const ldb_table* b
       names.push_back("set_side");
       data_bytes.push_back(0);
    }
-   TableGuard res(ctx);
+   LdbTableHold res(ctx);
    LDB_TRY(ldb_gpu_table_alloc(ctx, name, (int32_t) types.size(), types.data(), names.data(), n, data_bytes.data(), 0, &res.t));
    const int grid = ldb_grid_for(ctx, n + 1, 256, 8);
    for (int k = 0; k < nc; k++) {
@@ -150,17 +106,16 @@ static int32_t table_concat(ldb_ctx* ctx, const ldb_table* a, const ldb_table* b
       } else {
          const size_t w = (size_t) ca.width;
          if (dst.width != ca.width) { // (narrowed decimal inputs: keep the source width)
-            ldb_dev_free(ctx, dst.values);
-            dst.values = nullptr;
+            LdbBufs::drop(ctx, &dst.values);
             dst.width = ca.width;
             dst.value_bytes = n * (int64_t) w;
-            LDB_TRY(ldb_dev_alloc(ctx, &dst.values, (size_t) (dst.value_bytes ? dst.value_bytes : 8)));
+            LDB_TRY(LdbBufs::alloc_into(ctx, &dst.values, (size_t) dst.value_bytes));
          }
          if (na) LDB_HIP(hipMemcpyAsync(dst.values, ca.values, (size_t) na * w, hipMemcpyDeviceToDevice, ctx->stream));
          if (nb) LDB_HIP(hipMemcpyAsync((char*) dst.values + (size_t) na * w, cb.values, (size_t) nb * w, hipMemcpyDeviceToDevice, ctx->stream));
       }
       if (ca.validity || cb.validity) {
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &dst.validity, (size_t) ((n + 7) / 8 + 1)));
+         LDB_TRY(LdbBufs::alloc_into(ctx, &dst.validity, (size_t) ((n + 7) / 8 + 1)));
          hipLaunchKernelGGL(k_concat_validity, dim3(ldb_grid_for(ctx, (n + 7) / 8, 256, 8)), dim3(256), 0, ctx->stream, (const uint8_t*) ca.validity, (uint64_t) na,
                             (const uint8_t*) cb.validity, (uint64_t) nb, dst.validity);
          dst.null_count = ca.null_count + cb.null_count;
@@ -205,7 +160,7 @@ __global__ void k_expand_groups(const uint32_t* __restrict__ off, uint64_t n_gro
 extern "C" int32_t ldb_gpu_set_op(ldb_ctx* ctx, ldb_rel* left, const ldb_colref* left_cols, ldb_rel* right, const ldb_colref* right_cols, int32_t n_cols, int32_t op, ldb_table** out) {
    if (!ctx || !left || !right || !left_cols || !right_cols || !out || n_cols < 1 || n_cols > LDB_MAX_KEYS) LDB_FAIL(LDB_ERR_INVALID, "set_op: bad argument (1..%d columns)", LDB_MAX_KEYS);
    if (op < LDB_SET_UNION_ALL || op > LDB_SET_EXCEPT_ALL) LDB_FAIL(LDB_ERR_INVALID, "set_op: bad operation %d", op);
-   TableGuard a(ctx), b(ctx), u(ctx), g(ctx);
+   LdbTableHold a(ctx), b(ctx), u(ctx), g(ctx);
    LDB_TRY(ldb_gpu_materialize(ctx, left, left_cols, n_cols, &a.t));
    LDB_TRY(ldb_gpu_materialize(ctx, right, right_cols, n_cols, &b.t));
    LDB_TRY(table_concat(ctx, a.t, b.t, op != LDB_SET_UNION_ALL, "set_op_input", &u.t));
@@ -214,7 +169,7 @@ extern "C" int32_t ldb_gpu_set_op(ldb_ctx* ctx, ldb_rel* left, const ldb_colref*
       return LDB_OK;
    }
    // ONE aggregation over all columns with a counter per input side (the map with two i64 counters)
-   RelGuard ur(ctx);
+   LdbRelHold ur(ctx);
    LDB_TRY(ldb_gpu_rel_from_table(ctx, u.t, &ur.r));
    std::vector<ldb_colref> keys;
    for (int32_t k = 0; k < n_cols; k++) keys.push_back({0, k});
@@ -231,7 +186,7 @@ extern "C" int32_t ldb_gpu_set_op(ldb_ctx* ctx, ldb_rel* left, const ldb_colref*
    }
    LDB_TRY(ldb_gpu_groupby(ctx, ur.r, nullptr, 0, keys.data(), n_cols, aggs, 2, std::max<int64_t>(16, u.t->n_rows), &g.t));
    const int64_t ng = g.t->n_rows;
-   Bufs bufs(ctx);
+   LdbBufs bufs(ctx);
    uint32_t *mult, *off, *sel;
    LDB_TRY(bufs.alloc(&mult, 4 * (size_t) (ng + 1)));
    LDB_TRY(bufs.alloc(&off, 4 * (size_t) (ng + 1)));
@@ -248,9 +203,9 @@ extern "C" int32_t ldb_gpu_set_op(ldb_ctx* ctx, ldb_rel* left, const ldb_colref*
    LDB_TRY(bufs.alloc(&sel, 4 * (size_t) (total ? total : 1)));
    if (total) hipLaunchKernelGGL(k_expand_groups, dim3(ldb_grid_for(ctx, (int64_t) total, 256, 8)), dim3(256), 0, ctx->stream, (const uint32_t*) off, (uint64_t) ng, total, sel);
    LDB_HIP(hipGetLastError());
-   RelGuard gr(ctx), picked(ctx);
+   LdbRelHold gr(ctx), picked(ctx);
    LDB_TRY(ldb_gpu_rel_from_table(ctx, g.t, &gr.r));
-   bufs.forget(sel); // ldb_rel_select takes the selection vector over
+   bufs.keep(sel); // ldb_rel_select takes the selection vector over
    LDB_TRY(ldb_rel_select(ctx, gr.r, sel, (int64_t) total, &picked.r));
    LDB_TRY(ldb_gpu_materialize(ctx, picked.r, keys.data(), n_cols, out));
    return LDB_OK;
@@ -418,14 +373,16 @@ extern "C" int32_t ldb_gpu_window(ldb_ctx* ctx, ldb_rel* in, const ldb_colref* p
    std::vector<ldb_sort_spec> specs;
    for (int32_t k = 0; k < n_part; k++) specs.push_back({part_keys[k], 0, 0});
    for (int32_t k = 0; k < n_order; k++) specs.push_back(order[k]);
-   RelGuard sorted(ctx);
+   LdbRelHold sorted(ctx);
    if (!specs.empty()) {
       LDB_TRY(ldb_gpu_sort(ctx, in, specs.data(), (int32_t) specs.size(), &sorted.r));
    } else { // no PARTITION BY, no ORDER BY: one partition in input order
+      LdbBufs ib(ctx);
       uint32_t* iota;
-      LDB_TRY(ldb_dev_alloc(ctx, (void**) &iota, 4 * (size_t) (in->n_rows ? in->n_rows : 1)));
+      LDB_TRY(ib.alloc(&iota, 4 * (size_t) (in->n_rows ? in->n_rows : 1)));
       if (in->n_rows) hipLaunchKernelGGL(k_window_iota, dim3(ldb_grid_for(ctx, in->n_rows, 256, 8)), dim3(256), 0, ctx->stream, iota, (uint64_t) in->n_rows);
       LDB_HIP(hipGetLastError());
+      ib.keep(iota); // ldb_rel_select takes the vector over
       LDB_TRY(ldb_rel_select(ctx, in, iota, in->n_rows, &sorted.r));
    }
    const int64_t n = sorted.r->n_rows;
@@ -464,15 +421,14 @@ extern "C" int32_t ldb_gpu_window(ldb_ctx* ctx, ldb_rel* in, const ldb_colref* p
       }
       if (fn == LDB_WIN_COUNT) LDB_TRY(ldb_make_dcol(sorted.r, fns[f].col, &d->col[f]));
    }
-   TableGuard res(ctx);
+   LdbTableHold res(ctx);
    LDB_TRY(ldb_gpu_table_alloc(ctx, "window", n_fns, types.data(), names.data(), n, nullptr, 0, &res.t));
    if (n == 0) {
-      *out_rel = sorted.r;
-      sorted.r = nullptr;
+      *out_rel = sorted.release();
       *out_cols = res.release();
       return LDB_OK;
    }
-   Bufs bufs(ctx);
+   LdbBufs bufs(ctx);
    // 3. partitions: head flags → partition numbers and start rows
    uint32_t *head, *pos, *seg, *starts;
    LDB_TRY(bufs.alloc(&head, 4 * (size_t) n));
@@ -540,7 +496,7 @@ extern "C" int32_t ldb_gpu_window(ldb_ctx* ctx, ldb_rel* in, const ldb_colref* p
       LDB_HIP(hipMemsetAsync(d_nulls, 0, 8 * vf.size(), ctx->stream));
       for (size_t v = 0; v < vf.size(); v++) {
          ldb_column& oc = res.t->cols[(size_t) vf[v]];
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &oc.validity, (size_t) ((n + 7) / 8 + 1)));
+         LDB_TRY(LdbBufs::alloc_into(ctx, &oc.validity, (size_t) ((n + 7) / 8 + 1)));
          hipLaunchKernelGGL(k_win_pack_validity, dim3(ldb_grid_for(ctx, (n + 7) / 8, 256, 8)), dim3(256), 0, ctx->stream, (const uint8_t*) ok_bytes[(size_t) vf[v]], (uint64_t) n, oc.validity,
                             d_nulls + v);
       }
@@ -550,14 +506,12 @@ extern "C" int32_t ldb_gpu_window(ldb_ctx* ctx, ldb_rel* in, const ldb_colref* p
          ldb_column& oc = res.t->cols[(size_t) vf[v]];
          oc.null_count = (int64_t) nulls[v];
          if (!nulls[v]) { // no NULL after all: drop the bitmap
-            ldb_dev_free(ctx, oc.validity);
-            oc.validity = nullptr;
+            LdbBufs::drop(ctx, &oc.validity);
          }
       }
    }
    LDB_HIP(hipGetLastError());
-   *out_rel = sorted.r;
-   sorted.r = nullptr;
+   *out_rel = sorted.release();
    *out_cols = res.release();
    return LDB_OK;
 }

@@ -132,15 +132,18 @@ int32_t ldb_gather_column(ldb_ctx* ctx, const ldb_rel* r, ldb_colref ref, ldb_co
 // stable LSD sort of `perm` (n entries) by `words`-word records, digits [bit_lo, bit_hi) of each word
 // `varmask` (host, one word per record word, may be NULL): bits that differ between some two
 // records — a digit whose bits are all constant is skipped (an LSD pass over it is the identity).
-static int32_t radix_sort_perm(ldb_ctx* ctx, const uint64_t* keys, int words, uint32_t** perm_io, uint64_t n, int first_word, int last_word, int bits_lo, int bits_hi,
+// *perm_io is a block of `owner`; the passes alternate between it and a second vector taken from `owner` too — the one that does not hold
+// the result in the end is freed.
+static int32_t radix_sort_perm(ldb_ctx* ctx, LdbBufs& owner, const uint64_t* keys, int words, uint32_t** perm_io, uint64_t n, int first_word, int last_word, int bits_lo, int bits_hi,
                                const uint64_t* varmask) {
    if (n < 2) return LDB_OK;
    const uint64_t n_threads = (n + CS_CHUNK - 1) / CS_CHUNK;
    const int grid = (int) ((n_threads + CS_BLOCK - 1) / CS_BLOCK);
+   LdbBufs tmp(ctx);
    uint32_t *counts, *offsets, *perm_b;
-   LDB_TRY(ldb_dev_alloc(ctx, (void**) &counts, 4 * 16 * (size_t) n_threads));
-   LDB_TRY(ldb_dev_alloc(ctx, (void**) &offsets, 4 * 16 * (size_t) n_threads));
-   LDB_TRY(ldb_dev_alloc(ctx, (void**) &perm_b, 4 * (size_t) n));
+   LDB_TRY(tmp.alloc(&counts, 4 * 16 * (size_t) n_threads));
+   LDB_TRY(tmp.alloc(&offsets, 4 * 16 * (size_t) n_threads));
+   LDB_TRY(owner.alloc(&perm_b, 4 * (size_t) n));
    uint32_t* a = *perm_io;
    uint32_t* b = perm_b;
    for (int w = last_word; w >= first_word; w--) {
@@ -154,9 +157,7 @@ static int32_t radix_sort_perm(ldb_ctx* ctx, const uint64_t* keys, int words, ui
    }
    LDB_HIP(hipGetLastError());
    *perm_io = a;
-   ldb_dev_free(ctx, b);
-   ldb_dev_free(ctx, counts);
-   ldb_dev_free(ctx, offsets);
+   owner.free(b);
    return LDB_OK;
 }
 
@@ -307,20 +308,21 @@ __global__ void k_sel_expand(const uint64_t* __restrict__ bitmap, const uint32_t
 
 // the k smallest records (all of them when k >= n), sorted: *perm_out holds >= min(k, n) row numbers
 static int32_t sort_records(ldb_ctx* ctx, const uint64_t* keys, int words, uint64_t n, uint64_t k, uint32_t** perm_out) {
+   LdbBufs own(ctx); // the permutation, until the caller takes it
    uint32_t* perm;
    const int grid = ldb_grid_for(ctx, (int64_t) n, 256, 8);
    uint64_t m = n; // rows to sort
    std::vector<uint64_t> varmask((size_t) words, ~0ull);
    if (n > SS_MAX) {
+      LdbBufs tmp(ctx);
       unsigned long long* d_bits;
       std::vector<unsigned long long> init((size_t) (2 * words), 0ull), bits((size_t) (2 * words));
       for (int w = 0; w < words; w++) init[(size_t) (words + w)] = ~0ull;
-      LDB_TRY(ldb_dev_alloc(ctx, (void**) &d_bits, 16 * (size_t) words));
+      LDB_TRY(tmp.alloc(&d_bits, 16 * (size_t) words));
       LDB_TRY(ldb_h2d_small(ctx, d_bits, init.data(), 16 * (size_t) words)); // (pinned staging, never a pageable source inside a plan)
       // few blocks: every wave ends in two same-address atomics (≈10 ns each when contended)
       hipLaunchKernelGGL(k_key_bits, dim3(std::min(grid, 64), words), dim3(256), 0, ctx->stream, keys, words, n, d_bits);
       LDB_TRY(LDB_READBACK(ctx, bits.data(), d_bits, 16 * (size_t) words));
-      ldb_dev_free(ctx, d_bits);
       for (int w = 0; w < words; w++) varmask[(size_t) w] = bits[(size_t) w] ^ bits[(size_t) (words + w)];
    }
    if (k < n && n > SS_MAX) {
@@ -341,10 +343,11 @@ static int32_t sort_records(ldb_ctx* ctx, const uint64_t* keys, int words, uint6
       h_state.rank = h_state.rank0 = k ? k - 1 : 0;
       h_state.cand = n;
       LdbDesc<SelState> state_desc(ctx);
+      LdbBufs tmp(ctx);
       uint32_t* hist;
       LDB_TRY(state_desc.upload(&h_state, sizeof(h_state), false)); // (k_sel_pick updates it)
       SelState* state = state_desc.p;
-      LDB_TRY(ldb_dev_alloc(ctx, (void**) &hist, 4 * 256));
+      LDB_TRY(tmp.alloc(&hist, 4 * 256));
       LDB_HIP(hipMemsetAsync(hist, 0, 4 * 256, ctx->stream));
       // Passes stop as soon as what they leave — the rows below the k-th prefix + the rows sharing it — fits the one-workgroup sort (round 6: all
       // eight passes, sixteen launches, ran whatever the data; two or three bytes decide most of TPC-H's top-k inputs).  The count is an ordinary
@@ -366,29 +369,25 @@ static int32_t sort_records(ldb_ctx* ctx, const uint64_t* keys, int words, uint6
       const uint64_t n_words = (n + 63) / 64;
       uint64_t* bitmap;
       uint32_t *pop, *off;
-      LDB_TRY(ldb_dev_alloc(ctx, (void**) &bitmap, 8 * (size_t) n_words));
-      LDB_TRY(ldb_dev_alloc(ctx, (void**) &pop, 4 * (size_t) n_words));
-      LDB_TRY(ldb_dev_alloc(ctx, (void**) &off, 4 * (size_t) n_words));
+      LDB_TRY(tmp.alloc(&bitmap, 8 * (size_t) n_words));
+      LDB_TRY(tmp.alloc(&pop, 4 * (size_t) n_words));
+      LDB_TRY(tmp.alloc(&off, 4 * (size_t) n_words));
       hipLaunchKernelGGL(k_sel_flags, dim3(grid), dim3(256), 0, ctx->stream, keys, words, n, sel_words, (const SelState*) state, bitmap, pop);
       uint64_t* d_total;
       LDB_TRY(ldb_counters(ctx, 1, &d_total));
       LDB_TRY(ldb_exclusive_scan_u32(ctx, pop, off, (int64_t) n_words, d_total));
       LDB_TRY(ldb_read_u64(ctx, d_total, &m));
-      LDB_TRY(ldb_dev_alloc(ctx, (void**) &perm, 4 * (size_t) (m ? m : 1)));
+      LDB_TRY(own.alloc(&perm, 4 * (size_t) (m ? m : 1)));
       hipLaunchKernelGGL(k_sel_expand, dim3(grid), dim3(256), 0, ctx->stream, (const uint64_t*) bitmap, (const uint32_t*) off, perm, n_words, (uint64_t) (m ? m : 1));
       LDB_HIP(hipGetLastError());
-      state_desc.release();
-      ldb_dev_free(ctx, hist);
-      ldb_dev_free(ctx, bitmap);
-      ldb_dev_free(ctx, pop);
-      ldb_dev_free(ctx, off);
    } else {
-      LDB_TRY(ldb_dev_alloc(ctx, (void**) &perm, 4 * (size_t) (n ? n : 1)));
+      LDB_TRY(own.alloc(&perm, 4 * (size_t) (n ? n : 1)));
       if (n) hipLaunchKernelGGL(k_iota, dim3(grid), dim3(256), 0, ctx->stream, perm, n);
    }
    if (m > 1 && m <= SS_MAX) hipLaunchKernelGGL(k_small_sort, dim3(1), dim3(SS_BLOCK), 0, ctx->stream, keys, words, perm, (uint32_t) m);
-   else LDB_TRY(radix_sort_perm(ctx, keys, words, &perm, m, 0, words - 1, 0, 64, varmask.data()));
+   else LDB_TRY(radix_sort_perm(ctx, own, keys, words, &perm, m, 0, words - 1, 0, 64, varmask.data()));
    LDB_HIP(hipGetLastError());
+   own.keep(perm);
    *perm_out = perm;
    return LDB_OK;
 }
@@ -443,17 +442,15 @@ static int32_t sort_perm(ldb_ctx* ctx, ldb_rel* in, const ldb_sort_spec* specs, 
       off += sp.nbytes;
    }
    h->words = (off + 7) / 8;
+   LdbBufs tmp(ctx);
    uint64_t* keys;
-   LDB_TRY(ldb_dev_alloc(ctx, (void**) &keys, 8 * (size_t) h->words * (size_t) (n ? n : 1)));
+   LDB_TRY(tmp.alloc(&keys, 8 * (size_t) h->words * (size_t) (n ? n : 1)));
    LdbDesc<DSort> d_desc(ctx);
    LDB_TRY(d_desc.upload(h, sizeof(*h)));
    DSort* d = d_desc.p;
    if (n) hipLaunchKernelGGL(k_sort_keys, dim3(grid), dim3(256), 0, ctx->stream, d, keys);
    LDB_HIP(hipGetLastError());
-   LDB_TRY(sort_records(ctx, keys, h->words, n, k, perm_out));
-   d_desc.release();
-   ldb_dev_free(ctx, keys);
-   return LDB_OK;
+   return sort_records(ctx, keys, h->words, n, k, perm_out);
 }
 
 extern "C" int32_t ldb_gpu_sort(ldb_ctx* ctx, ldb_rel* in, const ldb_sort_spec* specs, int32_t n_specs, ldb_rel** out) {
@@ -495,9 +492,10 @@ extern "C" int32_t ldb_gpu_partition(ldb_ctx* ctx, ldb_rel* in, const ldb_colref
    uint64_t* ids;
    uint32_t* perm;
    unsigned long long* hist;
-   LDB_TRY(ldb_dev_alloc(ctx, (void**) &ids, 8 * (size_t) (n ? n : 1)));
-   LDB_TRY(ldb_dev_alloc(ctx, (void**) &perm, 4 * (size_t) (n ? n : 1)));
-   LDB_TRY(ldb_dev_alloc(ctx, (void**) &hist, 8 * 256));
+   LdbBufs tmp(ctx);
+   LDB_TRY(tmp.alloc(&ids, 8 * (size_t) (n ? n : 1)));
+   LDB_TRY(tmp.alloc(&perm, 4 * (size_t) (n ? n : 1)));
+   LDB_TRY(tmp.alloc(&hist, 8 * 256));
    LDB_HIP(hipMemsetAsync(hist, 0, 8 * 256, ctx->stream));
    const int grid = ldb_grid_for(ctx, (int64_t) n, 256, 8);
    if (n) {
@@ -507,16 +505,15 @@ extern "C" int32_t ldb_gpu_partition(ldb_ctx* ctx, ldb_rel* in, const ldb_colref
    }
    LDB_HIP(hipGetLastError());
    // stable counting sort on the partition id (<= 8 bits → two 4-bit passes)
-   LDB_TRY(radix_sort_perm(ctx, ids, 1, &perm, n, 0, 0, 0, nparts > 16 ? 8 : 4, nullptr));
+   LDB_TRY(radix_sort_perm(ctx, tmp, ids, 1, &perm, n, 0, 0, 0, nparts > 16 ? 8 : 4, nullptr));
    std::vector<unsigned long long> hh(256);
    LDB_TRY(LDB_READBACK(ctx, hh.data(), hist, 8 * 256));
    for (int p = 0; p < nparts; p++) counts[p] = (int64_t) hh[(size_t) p];
    dk_desc.release();
-   ldb_dev_free(ctx, ids);
-   ldb_dev_free(ctx, hist);
-   ldb_rel* permuted;
-   LDB_TRY(ldb_rel_select(ctx, in, perm, (int64_t) n, &permuted));
-   int32_t s = ldb_gpu_materialize(ctx, permuted, cols, n_cols, out);
-   ldb_gpu_rel_release(ctx, permuted);
-   return s;
+   tmp.free(ids);
+   tmp.free(hist);
+   LdbRelHold permuted(ctx);
+   tmp.keep(perm); // (ldb_rel_select takes the permutation over)
+   LDB_TRY(ldb_rel_select(ctx, in, perm, (int64_t) n, &permuted.r));
+   return ldb_gpu_materialize(ctx, permuted.r, cols, n_cols, out);
 }

@@ -285,7 +285,7 @@ extern "C" int32_t ldb_gpu_tpch_generate(ldb_ctx* ctx, int32_t table_id, int64_t
    table_slice(table_id, n_orders, part, n_parts, &b, &e);
    const int64_t n = e - b;
    if (n >= (int64_t) LDB_NULL_ROW) LDB_FAIL(LDB_ERR_UNSUPPORTED, "tpch_generate: slice of %ld rows exceeds uint32 row ids; use more partitions", (long) n);
-   auto t = std::make_unique<ldb_table>();
+   LdbTableHold t(ctx, new ldb_table());
    t->ctx = ctx;
    t->name = tname;
    t->n_rows = n;
@@ -294,26 +294,28 @@ extern "C" int32_t ldb_gpu_tpch_generate(ldb_ctx* ctx, int32_t table_id, int64_t
    const int grid = ldb_grid_for(ctx, n, 256, 8);
    for (int c = 0; c < n_all; c++) {
       if (!((col_mask >> c) & 1)) continue;
-      ldb_column col;
+      t->cols.emplace_back(); // (the table owns the column's buffers from the start: an error return frees them with it)
+      ldb_column& col = t->cols.back();
       col.name = defs[c].name;
       col.type = defs[c].type;
       col.width = gen_width(table_id, c, col.type, narrow);
       if (col.type.type == LDB_T_UTF8 && table_id == LDB_TPCH_CUSTOMER && c == C_NAME) {
          col.value_bytes = n * LDB_TPCH_CNAME_LEN;
-         LDB_TRY(ldb_dev_alloc(ctx, &col.values, (size_t) col.value_bytes));
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &col.offsets, 8 * (size_t) (n + 1)));
+         LDB_TRY(LdbBufs::alloc_into(ctx, &col.values, (size_t) col.value_bytes));
+         LDB_TRY(LdbBufs::alloc_into(ctx, &col.offsets, 8 * (size_t) (n + 1)));
          hipLaunchKernelGGL(k_gen_cname, dim3(grid), dim3(256), 0, ctx->stream, b, (uint64_t) n, col.offsets, (char*) col.values);
       } else if (col.type.type == LDB_T_UTF8 && ldb_tpch_is_text(table_id, c)) { // p_brand, s_comment, o_comment, c_phone …
+         LdbBufs tmp(ctx);
          int64_t* lens;
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &lens, 8 * (size_t) (n + 1)));
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &col.offsets, 8 * (size_t) (n + 1)));
+         LDB_TRY(tmp.alloc(&lens, 8 * (size_t) (n + 1)));
+         LDB_TRY(LdbBufs::alloc_into(ctx, &col.offsets, 8 * (size_t) (n + 1)));
          if (n) hipLaunchKernelGGL(k_gen_text_lens, dim3(grid), dim3(256), 0, ctx->stream, table_id, (int32_t) c, b, (uint64_t) n, lens);
          LDB_TRY(ldb_exclusive_scan_i64(ctx, lens, col.offsets, n, col.offsets + n));
          uint64_t total = 0;
          LDB_TRY(ldb_read_u64(ctx, col.offsets + n, &total));
-         ldb_dev_free(ctx, lens);
+         tmp.free(lens);
          col.value_bytes = (int64_t) total;
-         LDB_TRY(ldb_dev_alloc(ctx, &col.values, (size_t) total));
+         LDB_TRY(LdbBufs::alloc_into(ctx, &col.values, (size_t) total));
          if (n) hipLaunchKernelGGL(k_gen_text_fill, dim3(grid), dim3(256), 0, ctx->stream, table_id, (int32_t) c, b, (uint64_t) n, (const int64_t*) col.offsets, (char*) col.values);
       } else if (col.type.type == LDB_T_UTF8 && ldb_tpch_wordcol_words(table_id, c)) { // p_name, p_type
          const int words = ldb_tpch_wordcol_words(table_id, c);
@@ -330,16 +332,17 @@ extern "C" int32_t ldb_gpu_tpch_generate(ldb_ctx* ctx, int32_t table_id, int64_t
             pos += (int) len;
          }
          dom.off[n_vocab] = pos;
+         LdbBufs tmp(ctx);
          int64_t* lens;
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &lens, 8 * (size_t) (n + 1)));
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &col.offsets, 8 * (size_t) (n + 1)));
+         LDB_TRY(tmp.alloc(&lens, 8 * (size_t) (n + 1)));
+         LDB_TRY(LdbBufs::alloc_into(ctx, &col.offsets, 8 * (size_t) (n + 1)));
          if (n) hipLaunchKernelGGL(k_gen_pname_lens, dim3(grid), dim3(256), 0, ctx->stream, dom, (int32_t) c, (int32_t) words, b, (uint64_t) n, lens);
          LDB_TRY(ldb_exclusive_scan_i64(ctx, lens, col.offsets, n, col.offsets + n));
          uint64_t total = 0;
          LDB_TRY(ldb_read_u64(ctx, col.offsets + n, &total));
-         ldb_dev_free(ctx, lens);
+         tmp.free(lens);
          col.value_bytes = (int64_t) total;
-         LDB_TRY(ldb_dev_alloc(ctx, &col.values, (size_t) total));
+         LDB_TRY(LdbBufs::alloc_into(ctx, &col.values, (size_t) total));
          if (n) hipLaunchKernelGGL(k_gen_pname_fill, dim3(grid), dim3(256), 0, ctx->stream, dom, (int32_t) c, (int32_t) words, b, (uint64_t) n, (const int64_t*) col.offsets, (char*) col.values);
       } else if (col.type.type == LDB_T_UTF8) {
          const char* const* strs = domain_strings(table_id, c);
@@ -354,25 +357,25 @@ extern "C" int32_t ldb_gpu_tpch_generate(ldb_ctx* ctx, int32_t table_id, int64_t
             pos += (int) len;
          }
          dom.off[dom.n] = pos;
+         LdbBufs tmp(ctx);
          int64_t* lens;
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &lens, 8 * (size_t) (n + 1)));
-         LDB_TRY(ldb_dev_alloc(ctx, (void**) &col.offsets, 8 * (size_t) (n + 1)));
+         LDB_TRY(tmp.alloc(&lens, 8 * (size_t) (n + 1)));
+         LDB_TRY(LdbBufs::alloc_into(ctx, &col.offsets, 8 * (size_t) (n + 1)));
          if (n) hipLaunchKernelGGL(k_gen_str_lens, dim3(grid), dim3(256), 0, ctx->stream, dom, table_id, c, b, (uint64_t) n, lens);
          LDB_TRY(ldb_exclusive_scan_i64(ctx, lens, col.offsets, n, col.offsets + n));
          uint64_t total = 0;
          LDB_TRY(ldb_read_u64(ctx, col.offsets + n, &total));
-         ldb_dev_free(ctx, lens);
+         tmp.free(lens);
          col.value_bytes = (int64_t) total;
-         LDB_TRY(ldb_dev_alloc(ctx, &col.values, (size_t) total));
+         LDB_TRY(LdbBufs::alloc_into(ctx, &col.values, (size_t) total));
          if (n) hipLaunchKernelGGL(k_gen_str_fill, dim3(grid), dim3(256), 0, ctx->stream, dom, table_id, c, b, (uint64_t) n, (const int64_t*) col.offsets, (char*) col.values);
       } else {
          col.value_bytes = n * col.width;
-         LDB_TRY(ldb_dev_alloc(ctx, &col.values, (size_t) col.value_bytes));
+         LDB_TRY(LdbBufs::alloc_into(ctx, &col.values, (size_t) col.value_bytes));
          g.values[c] = col.values;
          g.width[c] = col.width;
          g.mask |= 1ull << c;
       }
-      t->cols.push_back(col);
    }
    if (n && g.mask) {
       switch (table_id) {
@@ -389,7 +392,7 @@ extern "C" int32_t ldb_gpu_tpch_generate(ldb_ctx* ctx, int32_t table_id, int64_t
    }
    LDB_HIP(hipGetLastError());
    LDB_HIP(hipStreamSynchronize(ctx->stream));
-   LDB_TRY(ldb_table_dict_encode_all(ctx, t.get())); // as ldb_gpu_table_register does for imported tables
+   LDB_TRY(ldb_table_dict_encode_all(ctx, t.t)); // as ldb_gpu_table_register does for imported tables
    *out = t.release();
    return LDB_OK;
 }

@@ -821,6 +821,12 @@ class Context:
         check(self.lib.ldb_gpu_desc_cache_held(self.h, C.byref(held), C.byref(under)))
         return {"hits": h.value, "misses": m.value, "bytes": b.value, "held": held.value, "underflows": under.value}
 
+    def mem_stats(self):
+        """device blocks the context's allocator has handed out and not got back (descriptor-cache blocks apart), their bytes, and the bytes parked for reuse"""
+        n, b, p = C.c_int64(), C.c_int64(), C.c_int64()
+        check(self.lib.ldb_gpu_mem_stats(self.h, C.byref(n), C.byref(b), C.byref(p)))
+        return {"live_blocks": n.value, "live_bytes": b.value, "parked_bytes": p.value}
+
     def run_subop_dump(self, dump, tables, name="subop_dump", comm=None):
         """runs a query from the reference's sub-operator dump (tools/ct/mlir-subop-to-json.cpp output, text or path):
         translate_subop_dump → run_plan"""

@@ -257,6 +257,7 @@ GPU_API = {
     "ldb_gpu_trace_stats": (i32, [P, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
     "ldb_gpu_desc_cache_stats": (i32, [P, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
     "ldb_gpu_desc_cache_held": (i32, [P, C.POINTER(i64), C.POINTER(i64)]),
+    "ldb_gpu_mem_stats": (i32, [P, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
     "ldb_gpu_order_dependent_misses": (i64, []),
     "ldb_gpu_table_stamp": (u64, [P]),
     # include/ldb_tpchgen.h (device generator)
