@@ -345,7 +345,17 @@ typedef enum { LDB_RHS_INT = 0, LDB_RHS_STRING = 1, LDB_RHS_COLUMN = 2, LDB_RHS_
  *   ints, dates (days), char(1) (4 raw bytes as int32), decimals (unscaled at column scale)
  *   travel as a 128-bit integer (value_lo, value_hi); strings as (str, str_len).
  * rhs_kind = COLUMN compares two columns (residual predicates such as l_commitdate <
- * l_receiptdate that the reference evaluates in generated code). */
+ * l_receiptdate that the reference evaluates in generated code).
+ * Over a utf8 column an IN list may hold any number of string constants of any length (the empty
+ * string, duplicates and prefixes of one another included; n_in = 0 passes no row), and the
+ * constant of EQ … GTE may be of any length, as in the reference (a hash set of any size,
+ * Restrictions.cpp:481-515; std::string_view comparisons).  ldb_gpu_scan_filter, ldb_gpu_scan_count
+ * and the `preds` of ldb_gpu_groupby take such conjuncts; what the kernels' inline descriptor holds
+ * (<= 8 constants of <= 128 bytes in all, a constant of <= 48 bytes) is evaluated fused as before,
+ * anything larger by a pass of its own (see ldb_gpu_scan_filter).  Lists over other column types hold
+ * at most 8 constants, LIKE patterns at most 48 bytes; everywhere else a conjunct is accepted (the
+ * clauses of ldb_gpu_scan_filter_dnf, a join's anti_preds, conditional aggregates) the inline
+ * limits hold: LDB_ERR_UNSUPPORTED. */
 typedef struct {
    ldb_colref col;
    int32_t op; /* ldb_filter_op */
@@ -366,18 +376,33 @@ typedef struct {
 /* Replaces ScanBatchesTask::unitRun + Restrictions::applyFilters (LingoDBTable.cpp:382-407,
  * Restrictions.cpp:365-390): conjunction evaluated in descriptor order; the result relation
  * holds the passing rows in ascending row order (the order of the reference's selection
- * vectors inside a morsel, morsels in table order). */
+ * vectors inside a morsel, morsels in table order).
+ * A conjunct whose string constants the inline descriptor cannot hold (ldb_filter_desc) is a
+ * STRING-SET conjunct: the other conjuncts run first, in one pass, then each such conjunct as one pass
+ * of the string-set kernel over the survivors (sorted distinct constants, a binary search on 64-bit
+ * prefix keys per row).  It is never deferred: a lazy input is evaluated first and the result is
+ * materialised.  Option scan_strset_min_in (default 9) sends IN lists of at least that many string
+ * constants to that kernel even where the inline form could hold them; dictionary-encoded columns
+ * test their codes either way. */
 int32_t ldb_gpu_scan_filter(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_desc* preds, int32_t n_preds, ldb_rel** out);
 /* How a LIKE / NOT LIKE pattern will be matched (no device needed): *n_segments = 0 → the general matcher
  * (StringRuntime::like semantics: '_', escapes, non-ASCII); otherwise the pattern is ASCII literals separated
  * by '%' (≤ 4 of ≤ 16 bytes) and is matched by position inside the scan kernel — seg[2j], seg[2j+1] = start and
  * length of literal j in the pattern, *anchors bit 0 / bit 1 = no leading / trailing '%'. */
 int32_t ldb_gpu_like_plan(const char* pattern, int32_t len, int32_t* n_segments, int32_t* seg, int32_t* anchors);
+/* How a list of string constants is laid out for the string-set kernel (no device needed): order[j] = index
+ * in the input of the j-th DISTINCT constant in the reference's string order (unsigned bytes, then length; of
+ * equal constants the first listed), keys[j] = its first 8 bytes, big-endian, zero padded — monotone in that
+ * order but not strict ("ab" and "ab\0" share a key), *n_distinct = how many, *in_lds = 1 when a workgroup
+ * stages the keys and lengths in LDS (n_distinct <= *lds_max), 0 when it searches them in global memory.
+ * order / keys hold n entries; order, keys, in_lds and lds_max may be NULL. */
+int32_t ldb_gpu_strset_plan(const char* const* strs, const int32_t* lens, int32_t n, int32_t* order, uint64_t* keys, int32_t* n_distinct, int32_t* in_lds, int32_t* lds_max);
 
 /* Disjunctive normal form: rows satisfying (clause 0) OR (clause 1) OR …, each clause a conjunction
  * of clause_sizes[c] consecutive entries of `preds` (<= 4 clauses, <= 24 conjuncts in all) — TPC-H
  * Q19's three alternatives.  The reference evaluates such a predicate as generated residual code
- * (db.or of db.and trees); ascending row order as for ldb_gpu_scan_filter. */
+ * (db.or of db.and trees); ascending row order as for ldb_gpu_scan_filter.  A clause that
+ * holds a string-set conjunct (ldb_gpu_scan_filter) is refused: LDB_ERR_UNSUPPORTED naming the clause. */
 int32_t ldb_gpu_scan_filter_dnf(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_desc* preds, const int32_t* clause_sizes, int32_t n_clauses, ldb_rel** out);
 /* count only (no selection written) */
 int32_t ldb_gpu_scan_count(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_desc* preds, int32_t n_preds, int64_t* count);

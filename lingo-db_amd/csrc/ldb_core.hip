@@ -42,7 +42,7 @@ int64_t ldb_option(const char* name, int64_t dflt) {
 }
 extern "C" int32_t ldb_gpu_set_option(const char* name, int64_t value) {
    if (!name) LDB_FAIL(LDB_ERR_INVALID, "set_option: NULL name");
-   static const char* known[] = {"jit", "jit_min_rows", "lazy_filter", "lazy_min_rows", "join_ordered", "join_chained", "gb_ordered", "gb_sorted", "zone_maps", "zone_min_rows", "gb_direct", "gb_wgs_per_cu", "gb_partition", "gb_partition_min_rows", "join_radix", "join_radix_min_rows", "join_radix_min_table_bytes", "join_radix_part_bytes", "probe_batch", "debug_check", "join_direct", "join_rank", "join_coarse", "dict_encode", "dict_min_rows", "comm_transport", "comm_timeout_ms", "desc_cache", "desc_cache_mb", "plan_replay", "scan_single_pass", "lazy_strings", "lazy_strings_min_rows", "gb_partition_wc", "join_radix_wc", "join_radix_lds", "gb_dense_out", "gb_partition_values", "join_pair32", "gb_dense_keys", "jit_async", "jit_threads", "jit_disk_cache", "join_all_match", "topk_short_select", "gb_fits64", "join_coarse_fine", "join_coarse_filtered", "compact_wide_tiles", "compact_max_words", "join_fuse_max_conjuncts", "join_coarse_finest", "jit_min_rows_like", "scan_split", "jit_share_compiles"};
+   static const char* known[] = {"jit", "jit_min_rows", "lazy_filter", "lazy_min_rows", "join_ordered", "join_chained", "gb_ordered", "gb_sorted", "zone_maps", "zone_min_rows", "gb_direct", "gb_wgs_per_cu", "gb_partition", "gb_partition_min_rows", "join_radix", "join_radix_min_rows", "join_radix_min_table_bytes", "join_radix_part_bytes", "probe_batch", "debug_check", "join_direct", "join_rank", "join_coarse", "dict_encode", "dict_min_rows", "comm_transport", "comm_timeout_ms", "desc_cache", "desc_cache_mb", "plan_replay", "scan_single_pass", "lazy_strings", "lazy_strings_min_rows", "gb_partition_wc", "join_radix_wc", "join_radix_lds", "gb_dense_out", "gb_partition_values", "join_pair32", "gb_dense_keys", "jit_async", "jit_threads", "jit_disk_cache", "join_all_match", "topk_short_select", "gb_fits64", "join_coarse_fine", "join_coarse_filtered", "compact_wide_tiles", "compact_max_words", "join_fuse_max_conjuncts", "join_coarse_finest", "jit_min_rows_like", "scan_split", "jit_share_compiles", "scan_strset_min_in"};
    bool ok = false;
    for (const char* k : known) ok |= strcmp(k, name) == 0;
    if (!ok) LDB_FAIL(LDB_ERR_INVALID, "set_option: unknown option '%s'", name);
@@ -1458,12 +1458,12 @@ int32_t ldb_make_dpred(const ldb_rel* r, const ldb_filter_desc* p, DPred* out) {
       if (done) return LDB_OK;
    }
    if (p->op == LDB_F_IN) {
-      if (p->n_in < 0 || p->n_in > LDB_MAX_IN) LDB_FAIL(LDB_ERR_UNSUPPORTED, "filter: IN list of %d values (max %d)", p->n_in, LDB_MAX_IN);
+      if (p->n_in < 0 || p->n_in > LDB_MAX_IN) LDB_FAIL(LDB_ERR_UNSUPPORTED, "filter: IN list of %d values (max %d inline; a longer list over a utf8 column is evaluated by ldb_gpu_scan_filter alone)", p->n_in, LDB_MAX_IN);
       out->n_in = p->n_in;
       if (is_str) {
          int32_t pos = 0;
          for (int k = 0; k < p->n_in; k++) {
-            if (pos + p->in_str_lens[k] > (int32_t) sizeof(out->in_blob)) LDB_FAIL(LDB_ERR_UNSUPPORTED, "filter: IN string constants exceed %zu bytes", sizeof(out->in_blob));
+            if (pos + p->in_str_lens[k] > (int32_t) sizeof(out->in_blob)) LDB_FAIL(LDB_ERR_UNSUPPORTED, "filter: IN string constants exceed %zu bytes inline (ldb_gpu_scan_filter alone evaluates longer ones)", sizeof(out->in_blob));
             out->in_off[k] = pos;
             memcpy(out->in_blob + pos, p->in_strs[k], (size_t) p->in_str_lens[k]);
             pos += p->in_str_lens[k];
@@ -1484,7 +1484,7 @@ int32_t ldb_make_dpred(const ldb_rel* r, const ldb_filter_desc* p, DPred* out) {
       if (zt->n_rows >= ldb_option("zone_min_rows", 1 << 20)) LDB_TRY(ldb_column_zones(r->ctx, zt, p->col.col, &out->zmin, &out->zmax));
    }
    if (is_str) {
-      if (p->str_len < 0 || p->str_len > LDB_STR_INLINE) LDB_FAIL(LDB_ERR_UNSUPPORTED, "filter: string constant of %d bytes (max %d)", p->str_len, LDB_STR_INLINE);
+      if (p->str_len < 0 || p->str_len > LDB_STR_INLINE) LDB_FAIL(LDB_ERR_UNSUPPORTED, "filter: string constant of %d bytes (max %d inline; ldb_gpu_scan_filter alone compares longer ones, LIKE patterns excepted)", p->str_len, LDB_STR_INLINE);
       out->str_len = p->str_len;
       memcpy(out->str, p->str, (size_t) p->str_len);
       if (p->op == LDB_F_LIKE || p->op == LDB_F_NOT_LIKE) ldb_like_plan(out);

@@ -29,6 +29,7 @@
 #include "ldb_chain.h"
 #include "ldb_gb_kernel.h"
 #include "ldb_jit.h"
+#include "ldb_strset.h"
 #include <cmath>
 #include <algorithm>
 #include <memory>
@@ -460,6 +461,11 @@ extern "C" int32_t ldb_gpu_groupby(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_d
          any_str = any_str || s;
       }
    if (any_str && n_keys == 0) return gb_keyless_strings(ctx, in, preds, n_preds, aggs, n_aggs, is_str, str_ref, out);
+   if (ldb_strset_any(in, preds, n_preds)) { // a string-set conjunct is evaluated by the scan alone: filter first, aggregate the filtered relation
+      LdbRelHold filtered(ctx);
+      LDB_TRY(ldb_gpu_scan_filter(ctx, in, preds, n_preds, &filtered.r));
+      return ldb_gpu_groupby(ctx, filtered.r, nullptr, 0, keys, n_keys, aggs, n_aggs, est_groups, out);
+   }
    if (in->pending.size() + (size_t) n_preds > LDB_MAX_PREDS) LDB_TRY(ldb_rel_force(ctx, in)); // else: a lazy input's conjuncts are fused below
    if (n_keys == 0 && !in->pending.empty()) // key-less ANY needs a representative row that passed the filter: materialise a lazy input
       for (int32_t a = 0; a < n_aggs; a++)

@@ -13,6 +13,7 @@
 
 #include "ldb_scan_kernel.h"
 #include "ldb_jit.h"
+#include "ldb_strset.h"
 
 // generic ahead-of-time kernels (descriptor read from memory)
 __global__ __launch_bounds__(SCAN_BLOCK) void k_scan_bitmap(const DScan* __restrict__ d, uint64_t* __restrict__ bitmap, uint32_t* __restrict__ block_counts) {
@@ -204,6 +205,8 @@ static int32_t scan_run_with(ldb_ctx* ctx, int64_t n, LAUNCH launch, uint32_t** 
    return LDB_OK;
 }
 
+int32_t ldb_scan_run_launch(ldb_ctx* ctx, int64_t n, const ldb_scan_launch& launch, uint32_t** sel_out, uint64_t* total_out) { return scan_run_with(ctx, n, launch, sel_out, total_out); }
+
 // run the conjunction over the dense base rows of `in` → ascending row numbers (device, owned by caller)
 static int32_t scan_run(ldb_ctx* ctx, ldb_rel* in, const DScan& h, uint32_t** sel_out, uint64_t* total_out) {
    const int64_t n = in->n_rows;
@@ -257,7 +260,11 @@ extern "C" int32_t ldb_gpu_scan_filter_dnf(ldb_ctx* ctx, ldb_rel* in, const ldb_
    for (int32_t c = 0; c < n_clauses; c++) {
       if (clause_sizes[c] == 0) LDB_FAIL(LDB_ERR_INVALID, "scan_filter_dnf: clause %d is empty", c);
       if (clause_sizes[c] < 0 || total_preds + clause_sizes[c] > DNF_MAX_PREDS) LDB_FAIL(LDB_ERR_UNSUPPORTED, "scan_filter_dnf: more than %d conjuncts in all", DNF_MAX_PREDS);
-      for (int32_t p = 0; p < clause_sizes[c]; p++, total_preds++) LDB_TRY(ldb_make_dpred(in, &preds[total_preds], &hp->preds[total_preds]));
+      for (int32_t p = 0; p < clause_sizes[c]; p++, total_preds++) {
+         if (ldb_strset_wanted(in, &preds[total_preds]))
+            LDB_FAIL(LDB_ERR_UNSUPPORTED, "scan_filter_dnf: clause %d holds a string-set conjunct (an IN list or a string constant beyond the inline descriptor): only conjunctions (ldb_gpu_scan_filter) evaluate those", c);
+         LDB_TRY(ldb_make_dpred(in, &preds[total_preds], &hp->preds[total_preds]));
+      }
       hp->clause_end[c] = total_preds;
    }
    LdbDesc<DScanDnf> d_desc(ctx);
@@ -320,9 +327,39 @@ int32_t ldb_rel_force(ldb_ctx* ctx, ldb_rel* r) {
    return LDB_OK;
 }
 
+// A conjunction that holds string-set conjuncts (ldb_strset.hip): the ordinary conjuncts first, through the one-pass scan, then one pass of the
+// string-set kernel per such conjunct over the survivors (through their row ids).  Such a conjunct never travels lazily — no consumer's kernel
+// evaluates it — so a pending input is forced, as for a LIKE.  Every pass keeps the ascending row order.
+static int32_t scan_filter_strset(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_desc* preds, int32_t n_preds, ldb_rel** out) {
+   std::vector<ldb_filter_desc> plain, sets;
+   for (int32_t p = 0; p < n_preds; p++) (ldb_strset_wanted(in, &preds[p]) ? sets : plain).push_back(preds[p]);
+   LDB_TRY(ldb_rel_force(ctx, in));
+   LdbRelHold cur(ctx);
+   ldb_rel* r = in;
+   uint32_t* sel;
+   uint64_t total;
+   if (!plain.empty()) {
+      DScan h;
+      LDB_TRY(build_scan_desc(in, plain.data(), (int32_t) plain.size(), &h));
+      LDB_TRY(scan_run(ctx, in, h, &sel, &total));
+      LDB_TRY(ldb_rel_select(ctx, in, sel, (int64_t) total, &cur.r));
+      r = cur.r;
+   }
+   for (auto& p : sets) {
+      LDB_TRY(ldb_strset_run(ctx, r, &p, &sel, &total));
+      LdbRelHold next(ctx);
+      LDB_TRY(ldb_rel_select(ctx, r, sel, (int64_t) total, &next.r));
+      std::swap(cur.r, next.r); // (the relation before this pass is released with `next`)
+      r = cur.r;
+   }
+   *out = cur.release();
+   return LDB_OK;
+}
+
 extern "C" int32_t ldb_gpu_scan_filter(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_desc* preds, int32_t n_preds, ldb_rel** out) {
    if (!ctx || !in || !out) LDB_FAIL(LDB_ERR_INVALID, "scan_filter: NULL argument");
    if (n_preds < 0 || n_preds > LDB_MAX_PREDS) LDB_FAIL(LDB_ERR_UNSUPPORTED, "scan: %d predicates (max %d)", n_preds, LDB_MAX_PREDS);
+   if (ldb_strset_any(in, preds, n_preds)) return scan_filter_strset(ctx, in, preds, n_preds, out);
    if (!in->pending.empty() && in->pending.size() + (size_t) n_preds > LDB_MAX_PREDS) LDB_TRY(ldb_rel_force(ctx, in));
    // LIKE conjuncts are evaluated by the scan kernel, whose waves stage their 64 strings in LDS and
    // match by position (d_like_simple_wave); fused into a consumer they would run the row-wise
@@ -355,6 +392,12 @@ extern "C" int32_t ldb_gpu_scan_filter(ldb_ctx* ctx, ldb_rel* in, const ldb_filt
 
 extern "C" int32_t ldb_gpu_scan_count(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_desc* preds, int32_t n_preds, int64_t* count) {
    if (!ctx || !in || !count) LDB_FAIL(LDB_ERR_INVALID, "scan_count: NULL argument");
+   if (n_preds >= 0 && n_preds <= LDB_MAX_PREDS && ldb_strset_any(in, preds, n_preds)) { // the count of the filter's rows: the string-set kernel writes a selection
+      LdbRelHold f(ctx);
+      LDB_TRY(scan_filter_strset(ctx, in, preds, n_preds, &f.r));
+      *count = f->n_rows;
+      return LDB_OK;
+   }
    if (in->pending.size() + (size_t) (n_preds > 0 ? n_preds : 0) > LDB_MAX_PREDS) LDB_TRY(ldb_rel_force(ctx, in));
    DScan h;
    LDB_TRY(build_scan_desc(in, preds, n_preds, &h));

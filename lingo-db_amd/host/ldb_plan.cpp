@@ -311,7 +311,9 @@ struct Interp {
       ldb_coltype ct;
       check(ldb_gpu_table_coltype(sides[(size_t) d.col.side], d.col.col, &ct), "IN list (column type)");
       const size_t w = ct.type == LDB_T_INT32 || ct.type == LDB_T_DATE32 || ct.type == LDB_T_CHAR4 ? 4 : ct.type == LDB_T_INT64 ? 8 : 0;
-      if (!w) throw std::runtime_error("filter: an IN list of more than " + std::to_string(kMaxInConstants) + " constants over a column that is not a 4- or 8-byte integer / date / char(1)");
+      if (!w)
+         throw std::runtime_error("filter: an IN list of more than " + std::to_string(kMaxInConstants) +
+                                  " numeric constants over a column that is not a 4- or 8-byte integer / date / char(1) (string lists of any size go to the scan itself)");
       std::vector<uint8_t> buf(w * (size_t) d.n_in);
       for (int32_t k = 0; k < d.n_in; k++) memcpy(buf.data() + w * (size_t) k, &d.in_values[2 * k], w); // (little-endian low word of the 128-bit constant)
       ct.nullable = 0;
@@ -796,7 +798,8 @@ struct Interp {
          auto ps = preds(*sides, &st.at("preds"));
          // Limits of ONE scan_filter call that the reference's Restrictions do not have (round 6): a conjunction of more than eight conjuncts is applied
          // eight at a time (a conjunction may be evaluated in any order); an integer IN list of more than eight constants — Restrictions.cpp:481-515 keeps
-         // a hash set of any size — becomes what it is relationally: a semi join against the table of its constants
+         // a hash set of any size — becomes what it is relationally: a semi join against the table of its constants;
+         // a string IN list of any size, and a string constant of any length, go to scan_filter as they are (its string-set kernel)
          std::vector<ldb_filter_desc> plain, longIn;
          for (auto& d : ps) (d.op == LDB_F_IN && d.n_in > kMaxInConstants && d.in_values ? longIn : plain).push_back(d);
          ldb_rel* cur = in;

@@ -169,6 +169,7 @@ GPU_API = {
     "ldb_gpu_prof_enable": (i32, [P, i32]),
     "ldb_gpu_prof_marker": (i32, [P, i32]),
     "ldb_gpu_like_plan": (i32, [C.c_char_p, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+    "ldb_gpu_strset_plan": (i32, [C.POINTER(C.c_char_p), C.POINTER(i32), i32, C.POINTER(i32), C.POINTER(u64), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
     "ldb_gpu_prof_reset": (i32, [P]),
     "ldb_gpu_prof_get": (i32, [P, C.c_char_p, C.POINTER(i64), C.POINTER(C.c_double)]),
     "ldb_gpu_prof_get_max": (i32, [P, C.c_char_p, C.POINTER(C.c_double)]),
