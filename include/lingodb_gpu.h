@@ -491,6 +491,38 @@ int32_t ldb_gpu_map_expr(ldb_ctx* ctx, ldb_rel* in, const ldb_xinstr* prog, int3
  * (UTF-8) positions from 1 with the reference's legalisation of out-of-range arguments
  * (StringRuntime::substr, src/runtime/StringRuntime.cpp:292-319).  NULL in → NULL out. */
 int32_t ldb_gpu_map_substr(ldb_ctx* ctx, ldb_rel* in, ldb_colref col, int64_t from, int64_t for_len, const char* name, ldb_table** out);
+/* String expressions as computed columns: upper / lower / || / cast(int as varchar) / length — the runtime calls ToUpper,
+ * ToLower, Concatenate, StringRuntime::fromInt and StringLength of the reference (src/runtime/StringRuntime.cpp:396-432,
+ * :201-212, :272-290), each with the reference's semantics:
+ *   - concatenation is a concatenation of BYTES;
+ *   - the case mappings work byte by byte with std::toupper / std::tolower in the C locale: only a-z / A-Z change, every
+ *     byte >= 0x80 passes through, so multi-byte UTF-8 characters (ß, É …) are untouched;
+ *   - a window (from, for_len) on a COL part is StringRuntime::substr in CHARACTERS, exactly ldb_gpu_map_substr's, applied
+ *     BEFORE the case mapping; from = 1 and for_len = LDB_STR_WHOLE take the whole string without reading it;
+ *   - an INT part is StringRuntime::fromInt: plain decimal, a leading '-', no padding (INT64_MIN included).
+ * ldb_gpu_map_strcat gives one utf8 column: the parts of each row concatenated left to right; one COL part with
+ * LDB_SC_UPPER is upper(col), one with LDB_SC_NONE a copy.  A row with a NULL in any COL / INT part is NULL; the result is
+ * nullable when a COL / INT part is (a validity bitmap, or the NULL row ids of an outer join's padded side).
+ * Errors: n_parts < 1 or > LDB_MAX_STRPARTS is LDB_ERR_UNSUPPORTED naming the limit; a COL part over a column that is not
+ * utf8, an INT part over a column that is not int32 / int64, an unknown kind / strcase, and a strcase or a window on a
+ * CONST / INT part are LDB_ERR_INVALID naming the part index.  Constants may be of any length.  Offsets of the result are
+ * the library's 64-bit offsets. */
+#define LDB_MAX_STRPARTS 8
+#define LDB_STR_WHOLE INT64_MAX /* for_len: to the end of the string */
+typedef enum { LDB_SP_COL = 0, LDB_SP_CONST = 1, LDB_SP_INT = 2 } ldb_strpart_kind;
+typedef enum { LDB_SC_NONE = 0, LDB_SC_UPPER = 1, LDB_SC_LOWER = 2 } ldb_strcase;
+typedef struct {
+   int32_t kind; /* ldb_strpart_kind */
+   int32_t strcase; /* ldb_strcase; COL parts only */
+   ldb_colref col; /* COL: a utf8 column; INT: an int32 / int64 column */
+   const char* str; /* CONST: bytes (need not be NUL-terminated) */
+   int64_t str_len;
+   int64_t from, for_len; /* COL: StringRuntime::substr window in CHARACTERS, applied before the case mapping; 1 / LDB_STR_WHOLE = the whole string */
+} ldb_strpart;
+int32_t ldb_gpu_map_strcat(ldb_ctx* ctx, ldb_rel* in, const ldb_strpart* parts, int32_t n_parts, const char* name, ldb_table** out);
+/* StringRuntime::len: the number of UTF-8 characters (bytes that are not 10xxxxxx) of a utf8 column as an INT64 column;
+ * NULL in → NULL out. */
+int32_t ldb_gpu_map_strlen(ldb_ctx* ctx, ldb_rel* in, ldb_colref col, const char* name, ldb_table** out);
 /* `in` extended by a table of exactly ldb_gpu_rel_rows(in) rows as a new LAST side (identity row
  * ids); the table must outlive the relation. */
 int32_t ldb_gpu_rel_zip(ldb_ctx* ctx, ldb_rel* in, const ldb_table* t, ldb_rel** out);

@@ -33,6 +33,13 @@ namespace {
 using ldbjson::J;
 using ldbjson::JParser;
 namespace {
+// "case" of a concat part
+static int32_t strcaseOf(const std::string& c) {
+   if (c == "none") return LDB_SC_NONE;
+   if (c == "upper") return LDB_SC_UPPER;
+   if (c == "lower") return LDB_SC_LOWER;
+   throw std::runtime_error("plan: map concat: unknown case '" + c + "' (none, upper, lower)");
+}
 
 // ================================================================== environment
 struct Value {
@@ -1057,6 +1064,31 @@ struct Interp {
             check(ldb_gpu_map_column(ctx, in, resolve(*sides, st.s("col"), "map"), LDB_FN_EXTRACT_YEAR, as.c_str(), &t), "map extract_year");
          } else if (fn == "substr") {
             check(ldb_gpu_map_substr(ctx, in, resolve(*sides, st.s("col"), "map"), st.iOr("from", 1), st.iOr("for", 1 << 30), as.c_str(), &t), "map substr");
+         } else if (fn == "upper" || fn == "lower") { // ToUpper / ToLower: one column part under a case mapping
+            ldb_strpart p = {LDB_SP_COL, fn == "upper" ? LDB_SC_UPPER : LDB_SC_LOWER, resolve(*sides, st.s("col"), "map"), nullptr, 0, 1, LDB_STR_WHOLE};
+            check(ldb_gpu_map_strcat(ctx, in, &p, 1, as.c_str(), &t), ("map " + fn).c_str());
+         } else if (fn == "length") { // StringLength: UTF-8 characters
+            check(ldb_gpu_map_strlen(ctx, in, resolve(*sides, st.s("col"), "map"), as.c_str(), &t), "map length");
+         } else if (fn == "concat") { // Concatenate (flattened): constants, columns (window, case mapping), integers as text
+            std::vector<ldb_strpart> ps;
+            for (auto& e : st.at("parts").arr) {
+               ldb_strpart p = {LDB_SP_CONST, LDB_SC_NONE, {0, 0}, nullptr, 0, 1, LDB_STR_WHOLE};
+               if (const J* c = e.get("const")) {
+                  p.str = c->str.data(); // (the plan outlives the call)
+                  p.str_len = (int64_t) c->str.size();
+               } else if (e.get("int")) {
+                  p.kind = LDB_SP_INT;
+                  p.col = resolve(*sides, e.s("int"), "map concat");
+               } else {
+                  p.kind = LDB_SP_COL;
+                  p.col = resolve(*sides, e.s("col"), "map concat");
+                  p.strcase = strcaseOf(e.sOr("case", "none"));
+                  p.from = e.iOr("from", 1);
+                  p.for_len = e.iOr("for", LDB_STR_WHOLE);
+               }
+               ps.push_back(p);
+            }
+            check(ldb_gpu_map_strcat(ctx, in, ps.data(), (int32_t) ps.size(), as.c_str(), &t), "map concat");
          } else {
             XB b;
             const Scalar ty = compileX(*sides, st.at("expr"), b);
@@ -1558,6 +1590,39 @@ extern "C" int32_t ldb_plan_stats(const ldb_plan* p, int64_t* executions, int64_
 }
 extern "C" const char* ldb_plan_json_last_error(void) { return g_plan_json_err.c_str(); }
 
+// the `fn` forms of a map step: extract_year / substr / upper / lower / length over "col", concat over "parts"
+static void checkMapFn(const J& st, const std::string& out) {
+   const std::string& fn = st.s("fn");
+   if (fn == "extract_year" || fn == "substr" || fn == "upper" || fn == "lower" || fn == "length") {
+      (void) st.s("col");
+      return;
+   }
+   if (fn != "concat") {
+      if (!st.get("expr")) throw std::runtime_error("plan: map → '" + out + "': unknown fn '" + fn + "'");
+      return;
+   }
+   const J* parts = st.get("parts");
+   if (!parts || parts->kind != J::ARR) throw std::runtime_error("plan: map → '" + out + "': concat needs an array 'parts'");
+   if (parts->arr.empty() || parts->arr.size() > LDB_MAX_STRPARTS)
+      throw std::runtime_error("plan: map → '" + out + "': concat of " + std::to_string(parts->arr.size()) + " parts (1 to " + std::to_string(LDB_MAX_STRPARTS) + ")");
+   size_t k = 0;
+   for (auto& e : parts->arr) {
+      const std::string where = "plan: map → '" + out + "': concat part " + std::to_string(k++);
+      if (e.kind != J::OBJ) throw std::runtime_error(where + " must be an object");
+      const int given = (e.get("const") ? 1 : 0) + (e.get("col") ? 1 : 0) + (e.get("int") ? 1 : 0);
+      if (given != 1) throw std::runtime_error(where + " needs exactly one of 'const', 'col', 'int'");
+      if (e.get("const")) (void) e.s("const");
+      if (e.get("col")) (void) e.s("col");
+      if (e.get("int")) (void) e.s("int");
+      if (const J* c = e.get("case")) {
+         if (c->kind != J::STR) throw std::runtime_error(where + ": 'case' must be a string");
+         (void) strcaseOf(c->str);
+         if (!e.get("col") && c->str != "none") throw std::runtime_error(where + ": 'case' belongs to a 'col' part");
+      }
+      if ((e.get("from") || e.get("for")) && !e.get("col")) throw std::runtime_error(where + ": 'from' / 'for' belong to a 'col' part");
+   }
+}
+
 // Device-less check of a plan's structure (what an emitter can verify before shipping a plan): the text
 // parses, every step has a known "op" with its required fields, every value a step reads was named as an
 // input or produced by an earlier step, no value is produced twice, and the result is produced by a step.
@@ -1627,6 +1692,7 @@ extern "C" int32_t ldb_plan_json_check(const char* plan_json, const char* const*
             if (!known.count(st.s(r))) throw std::runtime_error("plan: step '" + op + "' → '" + out + "' reads '" + st.s(r) + "' before it exists");
          for (const char* f : sh->needs) (void) st.at(f);
          if (op == "map" && !st.get("expr") && !st.get("fn")) throw std::runtime_error("plan: map → '" + out + "' needs 'expr' or 'fn'");
+         if (op == "map" && st.get("fn")) checkMapFn(st, out);
          if (known.count(out)) throw std::runtime_error("plan: value '" + out + "' defined twice");
          known[out] = true;
          if (const J* mo = st.get("mark_out")) known[mo->str] = true;

@@ -10,7 +10,8 @@
 //
 //   get_external + scan                         → a base table relation; meta.filters → restrictions
 //   map                                         → column bindings (expressions are inlined into their consumers; runtime calls
-//                                                 ExtractYearFromDate / Substring → map fn, ConstLike → LIKE restrictions)
+//                                                 ExtractYearFromDate / Substring / ToUpper / ToLower / StringLength → map fn, a Concatenate
+//                                                 nest → map fn concat with its parts, ConstLike → LIKE restrictions)
 //   filter all_true                             → restrictions (conjunctions, IN, LIKE, DNF → filter_dnf, anything else → a computed
 //                                                 boolean column + `= true`) / the conjuncts of a hash join (keys, residuals, post-join filters)
 //   lookup(SimpleState) | lookup_or_insert(HashMap) + reduce [+ create_thread_local / merge]
@@ -389,7 +390,7 @@ struct Translator {
    // runtime calls nested inside an expression become columns first (the expression language is arithmetic / boolean only)
    ExprP materializeCalls(Stream& s, const ExprP& e, const std::string& hint) {
       if (e->kind != Expr::OP) return e;
-      if (e->name == "call" && (e->cmp == "ExtractYearFromDate" || e->cmp == "Substring")) return mk(Expr::COL, ensureCol(s, e, hint + "_f" + std::to_string(++nval)));
+      if (e->name == "call" && (e->cmp == "ExtractYearFromDate" || e->cmp == "Substring" || e->cmp == "ToUpper" || e->cmp == "ToLower" || e->cmp == "StringLength" || e->cmp == "Concatenate")) return mk(Expr::COL, ensureCol(s, e, hint + "_f" + std::to_string(++nval)));
       bool changed = false;
       std::vector<ExprP> args;
       for (auto& a : e->args) {
@@ -401,6 +402,34 @@ struct Translator {
       auto r = std::make_shared<Expr>(*e);
       r->args = args;
       return r;
+   }
+   // the operands of a Concatenate nest, left to right, as the parts of a `concat` map step: string constants, columns, a Substring with
+   // constant bounds of a column, ToUpper / ToLower of a column or of such a Substring; anything else has no device form
+   void concatParts(const ExprP& e, std::vector<std::string>& out) {
+      auto isCall = [](const ExprP& x, const char* fn, size_t n) { return x->kind == Expr::OP && x->name == "call" && x->cmp == fn && x->args.size() == n; };
+      if (isCall(e, "Concatenate", 2)) {
+         concatParts(e->args[0], out);
+         concatParts(e->args[1], out);
+         return;
+      }
+      if (e->kind == Expr::CONST_STR) {
+         out.push_back("{\"const\": " + quote(e->name) + "}");
+         return;
+      }
+      std::string mapping;
+      ExprP x = e;
+      if (isCall(x, "ToUpper", 1) || isCall(x, "ToLower", 1)) {
+         mapping = x->cmp == "ToUpper" ? ", \"case\": \"upper\"" : ", \"case\": \"lower\"";
+         x = x->args[0];
+      }
+      std::string window;
+      if (isCall(x, "Substring", 3) && stripCast(x->args[1])->kind == Expr::CONST_INT && stripCast(x->args[2])->kind == Expr::CONST_INT) {
+         window = ", \"from\": " + std::to_string(stripCast(x->args[1])->i) + ", \"for\": " + std::to_string(stripCast(x->args[2])->i);
+         x = x->args[0];
+      }
+      if (x->kind != Expr::COL) throw Unsupported(x->kind == Expr::OP ? "'" + (x->name == "call" ? x->cmp : x->name) + "' inside Concatenate has no device form" : "this operand of Concatenate has no device form");
+      use(x->name);
+      out.push_back("{\"col\": " + quote(x->name) + mapping + window + "}");
    }
    // a plain column holding `e` on the stream: a computed expression becomes a `map` step
    std::string ensureCol(Stream& s, const ExprP& e0, const std::string& hint) {
@@ -422,6 +451,18 @@ struct Translator {
             const std::string src = ensureCol(s, a0, hint + "_arg"); // StringRuntime::substr(str, from, len)
             flush(s);
             m.fields = {{"in", quote(s.rel)}, {"fn", "\"substr\""}, {"col", quote(src)}, {"from", std::to_string(stripCast(e->args[1])->i)}, {"for", std::to_string(stripCast(e->args[2])->i)}, {"as", quote(as)}};
+         } else if ((e->cmp == "ToUpper" || e->cmp == "ToLower" || e->cmp == "StringLength") && e->args.size() == 1) { // StringRuntime::toUpper / toLower / len over a column
+            const std::string src = ensureCol(s, a0, hint + "_arg");
+            flush(s);
+            m.fields = {{"in", quote(s.rel)}, {"fn", e->cmp == "ToUpper" ? "\"upper\"" : e->cmp == "ToLower" ? "\"lower\"" : "\"length\""}, {"col", quote(src)}, {"as", quote(as)}};
+         } else if (e->cmp == "Concatenate" && e->args.size() == 2) { // StringRuntime::concat, nested left or right: one part list
+            std::vector<std::string> parts;
+            concatParts(e, parts);
+            if (parts.size() > 8) throw Unsupported("a concatenation of " + std::to_string(parts.size()) + " parts (the device form takes 8)");
+            flush(s);
+            std::string list = "[";
+            for (size_t k = 0; k < parts.size(); k++) list += (k ? ", " : "") + parts[k];
+            m.fields = {{"in", quote(s.rel)}, {"fn", "\"concat\""}, {"parts", list + "]"}, {"as", quote(as)}};
          } else {
             throw Unsupported("runtime function '" + e->cmp + "' has no device form");
          }

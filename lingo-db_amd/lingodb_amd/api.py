@@ -97,6 +97,35 @@ def preds_array(plist):
     return arr, n, keeps
 
 
+_STRCASE = {None: capi.SC_NONE, "none": capi.SC_NONE, "upper": capi.SC_UPPER, "lower": capi.SC_LOWER}
+
+
+def str_parts(parts):
+    """parts of ldb_gpu_map_strcat: bytes / str = a constant; {"col": (side, col), "case": "upper" | "lower", "from": f,
+    "for": l} = a utf8 column, optionally a character window of it and a case mapping; {"int": (side, col)} = an int32 /
+    int64 column as decimal text; a capi.StrPart is taken as it is.  → (ctypes array, n, keepalive)"""
+    arr = (capi.StrPart * max(len(parts), 1))()
+    keep = []
+    for k, p in enumerate(parts):
+        if isinstance(p, capi.StrPart):
+            arr[k] = p
+            continue
+        sp = arr[k]
+        sp.from_, sp.for_len = 1, capi.STR_WHOLE
+        if isinstance(p, (bytes, str)):
+            b = p.encode() if isinstance(p, str) else p
+            keep.append(b)
+            sp.kind, sp.str, sp.str_len = capi.SP_CONST, b, len(b)
+        elif "int" in p:
+            sp.kind, sp.col = capi.SP_INT, colref(*p["int"])
+        else:
+            sp.kind, sp.col = capi.SP_COL, colref(*p["col"])
+            c = p.get("case")
+            sp.strcase = c if isinstance(c, int) else _STRCASE[c]
+            sp.from_, sp.for_len = int(p.get("from", 1)), int(p.get("for", capi.STR_WHOLE))
+    return arr, len(parts), keep
+
+
 def factor(a=0, b=0, col=None):
     f = Factor()
     f.has_col = 0 if col is None else 1
@@ -334,6 +363,25 @@ class Rel:
     def map_substr(self, col, start, length, name="substr"):
         t = C.c_void_p()
         check(self.ctx.lib.ldb_gpu_map_substr(self.ctx.h, self.h, colref(*col), start, length, name.encode(), C.byref(t)))
+        return Table(self.ctx, t)
+
+    def map_strcat(self, parts, name="strcat"):
+        """parts: see str_parts — one utf8 column, the parts of each row concatenated left to right"""
+        arr, n, keep = str_parts(parts)
+        t = C.c_void_p()
+        check(self.ctx.lib.ldb_gpu_map_strcat(self.ctx.h, self.h, arr, n, name.encode(), C.byref(t)))
+        return Table(self.ctx, t)
+
+    def map_upper(self, col, name="upper"):
+        return self.map_strcat([{"col": col, "case": "upper"}], name)
+
+    def map_lower(self, col, name="lower"):
+        return self.map_strcat([{"col": col, "case": "lower"}], name)
+
+    def map_strlen(self, col, name="length"):
+        """number of UTF-8 characters of a utf8 column as an int64 column"""
+        t = C.c_void_p()
+        check(self.ctx.lib.ldb_gpu_map_strlen(self.ctx.h, self.h, colref(*col), name.encode(), C.byref(t)))
         return Table(self.ctx, t)
 
     def scan_count(self, plist):

@@ -37,6 +37,11 @@ WIN_RANK, WIN_SUM, WIN_MIN, WIN_MAX, WIN_COUNT, WIN_COUNT_STAR = range(6)
 FRAME_UNBOUNDED_PRECEDING, FRAME_UNBOUNDED_FOLLOWING = -(2 ** 63), 2 ** 63 - 1
 # ldb_scalar_fn
 FN_EXTRACT_YEAR = 0
+# ldb_strpart_kind / ldb_strcase (ldb_gpu_map_strcat)
+LDB_MAX_STRPARTS = 8
+STR_WHOLE = 2 ** 63 - 1
+SP_COL, SP_CONST, SP_INT = range(3)
+SC_NONE, SC_UPPER, SC_LOWER = range(3)
 
 
 class ColType(C.Structure):
@@ -111,6 +116,10 @@ class XInstr(C.Structure):
 
 X_COL, X_CONST, X_ADD, X_SUB, X_MUL, X_SDIV, X_MUL_POW10, X_SDIV_POW10, X_NEG, X_CMP, X_AND, X_OR, X_NOT, X_SELECT, X_ISNULL, X_COALESCE, X_ROW = range(17)
 X_FCONST, X_FADD, X_FSUB, X_FMUL, X_FDIV, X_FCMP, X_I2F, X_F2I, X_FCVT = range(17, 26)
+
+
+class StrPart(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("strcase", C.c_int32), ("col", ColRef), ("str", C.c_char_p), ("str_len", C.c_int64), ("from_", C.c_int64), ("for_len", C.c_int64)]
 
 
 class CommStats(C.Structure):
@@ -214,6 +223,8 @@ GPU_API = {
     "ldb_gpu_scan_filter_dnf": (i32, [P, P, C.POINTER(FilterDesc), C.POINTER(i32), i32, PP]),
     "ldb_gpu_map_expr": (i32, [P, P, C.POINTER(XInstr), i32, ColType, C.c_char_p, PP]),
     "ldb_gpu_map_substr": (i32, [P, P, ColRef, i64, i64, C.c_char_p, PP]),
+    "ldb_gpu_map_strcat": (i32, [P, P, C.POINTER(StrPart), i32, C.c_char_p, PP]),
+    "ldb_gpu_map_strlen": (i32, [P, P, ColRef, C.c_char_p, PP]),
     "ldb_gpu_scan_count": (i32, [P, P, C.POINTER(FilterDesc), i32, C.POINTER(i64)]),
     "ldb_gpu_hash_keys": (i32, [P, P, C.POINTER(ColRef), i32, PP]),
     "ldb_gpu_map_column": (i32, [P, P, ColRef, i32, C.c_char_p, PP]),
