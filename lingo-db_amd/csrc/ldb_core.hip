@@ -1953,7 +1953,6 @@ int32_t ldb_gather_columns(ldb_ctx* ctx, const ldb_rel* r, const ldb_colref* ref
    LDB_HIP(hipGetLastError());
    return finish_lazy();
 }
-int32_t ldb_gather_column(ldb_ctx* ctx, const ldb_rel* r, ldb_colref ref, ldb_column* out) { return ldb_gather_columns(ctx, r, &ref, 1, out); }
 
 // writes a lazy utf8 column's strings out of its dictionary: string i = dictionary[code i] (a NULL code gives the empty string;
 // the column's validity bitmap is separate).  The column object is logically const (the same value, another representation).

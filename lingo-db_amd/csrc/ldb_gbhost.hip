@@ -257,15 +257,13 @@ __global__ void k_pack_valid_bytes(const uint8_t* __restrict__ bytes, uint8_t* _
 }
 
 // ---------------------------------------------------------------- host side
-int32_t ldb_rel_select(ldb_ctx* ctx, ldb_rel* in, uint32_t* sel, int64_t n_sel, ldb_rel** out);
-int32_t ldb_gather_columns(ldb_ctx* ctx, const ldb_rel* r, const ldb_colref* refs, int32_t n_cols, ldb_column* outs);
-
-static uint64_t next_pow2_u64(uint64_t v) {
-   uint64_t p = 1;
-   while (p < v) p <<= 1;
-   return p;
+static bool same_acc(const DAcc& a, const DAcc& b) {
+   if (a.kind != b.kind || a.n_cpreds != b.n_cpreds || a.count_rows != b.count_rows) return false;
+   for (int p = 0; p < a.n_cpreds; p++)
+      if (a.cpred[p] != b.cpred[p]) return false;
+   if (a.kind == ACC_COUNT && a.count_rows) return true;
+   return memcmp(&a.e, &b.e, sizeof(DExprG)) == 0;
 }
-
 struct GbBuilder {
    ldb_rel* in;
    DGroupBy* h;
@@ -337,20 +335,68 @@ struct GbBuilder {
       }
       return LDB_OK;
    }
+   // accumulator `a` of `words` 64-bit words, the first initialised to `init`; an equal one that exists already is reused
+   int32_t add_acc(DAcc& a, int words, uint64_t init, int32_t* idx) {
+      for (int k = 0; k < h->n_accs; k++)
+         if (same_acc(h->accs[k], a)) {
+            *idx = k;
+            return LDB_OK;
+         }
+      if (h->n_accs >= GB_MAX_ACCS || h->n_words + words > GB_MAX_WORDS) LDB_FAIL(LDB_ERR_UNSUPPORTED, "groupby: too many distinct accumulators");
+      a.word = h->n_words;
+      h->word_init[h->n_words] = init;
+      for (int k = 1; k < words; k++) h->word_init[h->n_words + k] = 0;
+      h->n_words += words;
+      h->accs[h->n_accs] = a;
+      *idx = h->n_accs++;
+      return LDB_OK;
+   }
+   // the group's row counter: COUNT(*) without predicates
+   int32_t add_rows_counter(int32_t* idx) {
+      DAcc rows;
+      memset(&rows, 0, sizeof(rows));
+      rows.kind = ACC_COUNT;
+      rows.count_rows = 1;
+      return add_acc(rows, 1, 0, idx);
+   }
+   // counter of the rows contributing to aggregate `sp` (accumulator `acc`): AVG divisor, and NULL-ness of SUM / MIN / MAX results
+   int32_t need_counter(const ldb_agg_spec& sp, const DAcc& acc, bool nullable, int32_t* idx) {
+      DAcc c = acc;
+      if (sp.fn == LDB_AGG_AVG && sp.has_count_expr) {
+         // merging partial (sum, count) states: the divisor is SUM(count_expr)
+         bool cn = false;
+         c.kind = ACC_SUM64;
+         c.count_rows = 0;
+         LDB_TRY(conv_expr(&sp.count_expr, &c.e, &cn));
+         if (c.e.is_float) LDB_FAIL(LDB_ERR_INVALID, "groupby: AVG count_expr must be an integer expression");
+         return add_acc(c, 1, 0, idx);
+      }
+      c.kind = ACC_COUNT;
+      c.count_rows = (!nullable && sp.fn != LDB_AGG_COUNT) ? 1 : 0;
+      if (c.count_rows) memset(&c.e, 0, sizeof(c.e));
+      return add_acc(c, 1, 0, idx);
+   }
+   // the predicates of a conditional aggregate, shared between the aggregates that name the same ones
+   int32_t add_cpreds(const ldb_agg_spec& sp, DAcc& acc) {
+      acc.n_cpreds = sp.n_preds;
+      for (int p = 0; p < sp.n_preds; p++) {
+         DPred dp;
+         LDB_TRY(ldb_make_dpred(in, &sp.preds[p], &dp));
+         int found = -1;
+         for (int k = 0; k < h->n_cpreds; k++)
+            if (!memcmp(&h->cpreds[k], &dp, sizeof(DPred))) found = k;
+         if (found < 0) {
+            if (h->n_cpreds >= GB_MAX_CPREDS) LDB_FAIL(LDB_ERR_UNSUPPORTED, "groupby: too many conditional-aggregate predicates");
+            h->cpreds[h->n_cpreds] = dp;
+            found = h->n_cpreds++;
+         }
+         acc.cpred[p] = found;
+      }
+      return LDB_OK;
+   }
 };
 
-static bool same_acc(const DAcc& a, const DAcc& b) {
-   if (a.kind != b.kind || a.n_cpreds != b.n_cpreds || a.count_rows != b.count_rows) return false;
-   for (int p = 0; p < a.n_cpreds; p++)
-      if (a.cpred[p] != b.cpred[p]) return false;
-   if (a.kind == ACC_COUNT && a.count_rows) return true;
-   return memcmp(&a.e, &b.e, sizeof(DExprG)) == 0;
-}
-
-// ---------------------------------------------------------------- MIN / MAX over utf8 columns
-// one selection row per aggregate: the row of the extreme string, LDB_NULL_ROW when every argument is NULL (ldb_strminmax.hip)
-int32_t ldb_str_minmax(ldb_ctx* ctx, const ldb_rel* in, const ldb_colref* cols, const int32_t* is_max, int32_t n, uint32_t** sel_out);
-
+// ---------------------------------------------------------------- MIN / MAX over utf8 columns (ldb_str_minmax, ldb_strminmax.hip)
 // Does the aggregate read a utf8 column?  The only such shape is MIN / MAX of the bare column (one term, one factor, a = 0, b = 1) with
 // a utf8 result and no predicates of its own; *ref = that column.
 static int32_t gb_str_arg(const ldb_rel* in, const ldb_agg_spec& sp, int32_t a, bool* is_str, ldb_colref* ref) {
@@ -445,6 +491,569 @@ static int32_t gb_keyless_strings(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_de
    return LDB_OK;
 }
 
+// ---------------------------------------------------------------- ldb_gpu_groupby: the phases (DESIGN.md §2 names them)
+// LDS table (S slots x R replicas inside a 60 KB budget, or none) and the global table's capacity: first guess (enlarged by a retry) and maximum
+struct GbGeometry {
+   size_t lds_bytes;
+   uint64_t est, cap, cap_max;
+};
+static GbGeometry gb_geometry(DGroupBy* h, int64_t est_groups, int64_t n_rows) {
+   GbGeometry g;
+   const size_t slot_bytes = 8 * (size_t) (1 + h->n_words);
+   const size_t lds_budget = 60 * 1024;
+   g.est = h->keyless ? 1 : est_groups > 0 ? (uint64_t) est_groups : 0;
+   uint32_t S = 1, R = 1;
+   h->use_lds = 1;
+   if (h->keyless) {
+      R = 64;
+   } else if (g.est == 0) {
+      while ((size_t) S * 2 * slot_bytes <= lds_budget && S < 4096) S <<= 1;
+   } else {
+      S = (uint32_t) std::max<uint64_t>(8, next_pow2_u64(g.est * 2));
+      if ((size_t) S * slot_bytes > lds_budget) {
+         // more groups than LDS can pre-aggregate: the hit rate of a small cache is poor when
+         // the input is not clustered, so go straight to the global table
+         for (S = 1; (size_t) S * 2 * slot_bytes <= lds_budget;) S <<= 1;
+         if (g.est > (uint64_t) S * 4) h->use_lds = 0;
+      } else {
+         while (R < 64 && (size_t) S * (R * 2) * slot_bytes <= lds_budget) R <<= 1;
+      }
+   }
+   h->lds_slots = S;
+   h->lds_reps = R;
+   g.lds_bytes = h->use_lds ? (size_t) S * R * slot_bytes : 0;
+   const uint64_t cap_guess = g.est ? g.est * 2 : std::min<uint64_t>((uint64_t) n_rows * 2, 1ull << 22);
+   g.cap_max = next_pow2_u64(std::max<uint64_t>(1024, (uint64_t) n_rows * 2));
+   g.cap = std::min(std::max<uint64_t>(1024, next_pow2_u64(cap_guess)), g.cap_max);
+   return g;
+}
+// one turn of the retry loop: the table, the control words and the device descriptor of this attempt
+struct GbAttempt {
+   LdbBufs table; // released when the attempt ends, on every path (an error return included)
+   uint64_t *gk = nullptr, *ga = nullptr;
+   uint64_t max_groups = 0; // upper bound of groups = min(cap, rows) (1 for keyless); the sorted path knows the exact number
+   unsigned long long* d_ctl = nullptr; // zeroed arena words, fresh ones per attempt (ldb_counters)
+   LdbDesc<DGroupBy> desc; // given back after the attempt's control words are read, and on every error return
+   explicit GbAttempt(ldb_ctx* ctx) : table(ctx), desc(ctx) {}
+};
+// what the attempt's flags ask for.  Anything but GB_DONE throws the attempt's outputs away (rare: the estimate was far too low).
+enum GbVerdict { GB_DONE, GB_RETRY_HASHED, GB_RETRY_LARGER };
+// what the phases of one call share
+struct GbState {
+   ldb_ctx* ctx;
+   ldb_rel* in;
+   const ldb_colref* keys;
+   int32_t n_keys;
+   const ldb_agg_spec* aggs;
+   int32_t n_aggs;
+   const std::vector<bool>& is_str; // aggregate a is a MIN / MAX over a dictionary string, str_ref[a] its column
+   const std::vector<ldb_colref>& str_ref;
+   DGroupBy* h;
+   GbBuilder b;
+   LdbBufs sorted_tmp; // the sorted path's chunk counts / offsets
+   LdbBufs outs; // outputs of the current attempt: the survivors are kept into the result table, a failed attempt's are freed as a whole
+   std::vector<ldb_coltype> otypes; // result column types (their widths: DOut::out_width)
+   GbGeometry g{};
+   unsigned __int128 key_range = 0; // ordered / direct slots: number of key values
+   const ldb_column* direct_src = nullptr; // the key column where the kernels write the output keys themselves (direct slots; sorted keys with dense_keys)
+   uint32_t* chunk_off = nullptr;
+   uint64_t sorted_groups = 0, sorted_chunks = 0; // dense_sorted: number of groups / of 64-row chunks
+   uint64_t* d_sorted_groups = nullptr; // the same count on the device (an arena word)
+   void* direct_keys = nullptr;
+   uint32_t* rep_rows = nullptr;
+   std::vector<void*> out_vals;
+   std::vector<uint8_t*> out_valid, bitmaps;
+   // One control block per call, read back ONCE per attempt: [0] the kernel's overflow / long-probe flags, [1] the number of groups (total of
+   // the occupancy scan), [2 + a] NULLs of aggregate a.
+   unsigned long long ctl[2 + GB_MAX_OUT];
+   void forget_outputs() {
+      rep_rows = nullptr;
+      direct_keys = nullptr;
+      out_vals.assign((size_t) n_aggs, nullptr);
+      out_valid = bitmaps = std::vector<uint8_t*>((size_t) n_aggs, nullptr);
+   }
+   bool any_fn() const { return std::any_of(aggs, aggs + n_aggs, [](const ldb_agg_spec& a) { return a.fn == LDB_AGG_ANY; }); }
+   // aggregate a → its accumulators (h->accs, h->cpreds, h->word_init), its output descriptor h->outs[a] and its result column type
+   int32_t lower_agg(int32_t a) {
+      const ldb_agg_spec& sp = aggs[a];
+      DOut& o = h->outs[a];
+      memset(&o, 0, sizeof(o));
+      o.fn = sp.fn;
+      o.wide = sp.wide;
+      o.avg_pow10 = sp.avg_pow10;
+      o.acc = o.cnt_acc = o.cnt_rows_acc = o.cnt_pass_acc = -1;
+      o.is_float = sp.arg.is_float && sp.fn != LDB_AGG_COUNT && sp.fn != LDB_AGG_COUNT_STAR;
+      if (sp.n_preds < 0 || sp.n_preds > LDB_MAX_AGG_PREDS) LDB_FAIL(LDB_ERR_INVALID, "groupby: aggregate %d has %d predicates", a, sp.n_preds);
+      if (sp.avg_pow10 < 0 || sp.avg_pow10 > 38) LDB_FAIL(LDB_ERR_INVALID, "groupby: avg_pow10 %d", sp.avg_pow10);
+      DAcc acc;
+      memset(&acc, 0, sizeof(acc));
+      LDB_TRY(b.add_cpreds(sp, acc));
+      bool nullable = false;
+      const bool str = is_str[(size_t) a];
+      if (str) { // grouped: only a dictionary makes a string a fixed-width value (an arg-min accumulator in every layout is the follow-up)
+         const ldb_colref sr = str_ref[(size_t) a];
+         if (sr.col < 0 || (size_t) sr.col >= in->sides[(size_t) sr.side].table->cols.size()) LDB_FAIL(LDB_ERR_INVALID, "groupby: aggregate %d: column %d:%d out of range", a, sr.side, sr.col);
+         const ldb_column& sc = in->sides[(size_t) sr.side].table->cols[(size_t) sr.col];
+         if (!sc.dict_codes || !sc.dict) LDB_FAIL(LDB_ERR_UNSUPPORTED, "groupby: grouped MIN / MAX over a string column without a dictionary");
+         o.wide = 0;
+      }
+      b.str_codes = str;
+      if (sp.fn != LDB_AGG_COUNT_STAR) LDB_TRY(b.conv_expr(&sp.arg, &acc.e, &nullable));
+      b.str_codes = false;
+      o.e = acc.e;
+      const bool is_min = sp.fn == LDB_AGG_MIN;
+      switch (sp.fn) {
+         case LDB_AGG_COUNT_STAR:
+         case LDB_AGG_COUNT:
+            acc.kind = ACC_COUNT;
+            acc.count_rows = (sp.fn == LDB_AGG_COUNT_STAR || !nullable) ? 1 : 0;
+            if (acc.count_rows) memset(&acc.e, 0, sizeof(acc.e));
+            LDB_TRY(b.add_acc(acc, 1, 0, &o.acc));
+            break;
+         case LDB_AGG_SUM:
+         case LDB_AGG_AVG: {
+            acc.kind = sp.arg.is_float ? ACC_SUMF64 : sp.wide ? ACC_SUM128 : ACC_SUM64;
+            LDB_TRY(b.add_acc(acc, acc.kind == ACC_SUM128 ? 2 : 1, 0, &o.acc));
+            // a plain SUM over no non-NULL input is NULL; a conditional SUM (case … else 0) gets a
+            // non-NULL 0 from every row failing its predicates (see DOut::cnt_rows_acc)
+            if (sp.fn == LDB_AGG_AVG || nullable || (h->keyless && sp.n_preds == 0)) LDB_TRY(b.need_counter(sp, acc, nullable, &o.cnt_acc));
+            if (sp.fn == LDB_AGG_SUM && sp.n_preds > 0 && (nullable || h->keyless)) {
+               LDB_TRY(b.add_rows_counter(&o.cnt_rows_acc));
+               if (nullable) {
+                  DAcc passing = acc; // same predicates, counts rows
+                  passing.kind = ACC_COUNT;
+                  passing.count_rows = 1;
+                  memset(&passing.e, 0, sizeof(passing.e));
+                  LDB_TRY(b.add_acc(passing, 1, 0, &o.cnt_pass_acc));
+               }
+            }
+            break;
+         }
+         case LDB_AGG_MIN:
+         case LDB_AGG_MAX: {
+            const bool wide = sp.wide && !sp.arg.is_float && !str; // low word, signed high word, lock word (d_sink_minmax128)
+            const double inf = is_min ? __builtin_inf() : -__builtin_inf();
+            uint64_t init = is_min ? (uint64_t) INT64_MAX : (uint64_t) INT64_MIN;
+            if (sp.arg.is_float) memcpy(&init, &inf, 8);
+            acc.kind = wide ? (is_min ? ACC_MIN128 : ACC_MAX128) : sp.arg.is_float ? (is_min ? ACC_MINF64 : ACC_MAXF64) : (is_min ? ACC_MIN64 : ACC_MAX64);
+            LDB_TRY(b.add_acc(acc, wide ? 3 : 1, wide ? (is_min ? ~0ull : 0ull) : init, &o.acc));
+            if (wide) h->word_init[h->accs[o.acc].word + 1] = init; // (the lock word starts at 0)
+            if (nullable || h->keyless || sp.n_preds) LDB_TRY(b.need_counter(sp, acc, nullable, &o.cnt_acc));
+            break;
+         }
+         case LDB_AGG_ANY: // evaluated on the group's representative row
+            // the key-less group is pre-seeded with row 0 as its representative, which need not pass a fused filter
+            if (h->keyless && h->n_preds > 0) LDB_FAIL(LDB_ERR_UNSUPPORTED, "groupby: ANY in a key-less aggregation with fused predicates (filter the relation first)");
+            break;
+         default: LDB_FAIL(LDB_ERR_INVALID, "groupby: unknown aggregate function %d", sp.fn);
+      }
+      ldb_coltype ot{};
+      ot.type = sp.out_type;
+      ot.precision = sp.out_precision;
+      ot.scale = sp.out_scale;
+      ot.nullable = 1;
+      if (o.is_float) ot.type = LDB_T_FLOAT64;
+      if (sp.fn == LDB_AGG_COUNT || sp.fn == LDB_AGG_COUNT_STAR) ot.type = LDB_T_INT64;
+      if (str) ot.type = LDB_T_INT32; // the kernels write the winning code; the column becomes codes + the shared dictionary in result_table
+      int w = ldb_width_of(ot, 0);
+      if (w != 4 && w != 8 && w != 16) LDB_FAIL(LDB_ERR_INVALID, "groupby: aggregate %d output type %d unsupported", a, ot.type);
+      o.out_width = w;
+      otypes[(size_t) a] = ot;
+      return LDB_OK;
+   }
+   int32_t lower_aggs() {
+      h->n_outs = n_aggs;
+      otypes.resize((size_t) n_aggs);
+      for (int32_t a = 0; a < n_aggs; a++) LDB_TRY(lower_agg(a));
+      int32_t idx;
+      if (h->n_words == 0) LDB_TRY(b.add_rows_counter(&idx)); // at least one word so that every slot has something to initialise
+      return LDB_OK;
+   }
+   // sorted key column, no filter (DGroupBy::dense_sorted): number the groups by key changes — the heads pass, its scan and the read-back
+   int32_t sorted_layout(const ldb_column& kc) {
+      const int64_t n_rows = in->n_rows, n_chunks = (n_rows + 63) / 64;
+      uint32_t* chunk_cnt;
+      LDB_TRY(sorted_tmp.alloc(&chunk_cnt, 4 * (size_t) n_chunks));
+      LDB_TRY(sorted_tmp.alloc(&chunk_off, 4 * (size_t) n_chunks));
+      LdbDesc<DGroupBy> dh_desc(ctx);
+      LDB_TRY(dh_desc.upload(h, sizeof(*h)));
+      DGroupBy* dh = dh_desc.p;
+      {
+         const int hgrid = ldb_grid_for(ctx, n_rows, 256, 8);
+         hipFunction_t spec = nullptr;
+         std::string why;
+         if (ldb_jit_wanted(n_rows)) spec = ldb_jit_groupby_kernel(ctx->device, h, "k_gb_sorted_heads_spec", &why);
+         LdbProf prof_(ctx, "k_gb_sorted_heads");
+         if (spec) {
+            void* params[] = {(void*) &dh, (void*) &chunk_cnt};
+            LDB_HIP(hipModuleLaunchKernel(spec, (unsigned) hgrid, 1, 1, 256, 1, 1, 0, ctx->stream, params, nullptr));
+         } else {
+            hipLaunchKernelGGL(k_gb_sorted_heads, dim3(hgrid), dim3(256), 0, ctx->stream, dh, chunk_cnt);
+         }
+      }
+      LDB_TRY(ldb_counters(ctx, 1, &d_sorted_groups));
+      LDB_TRY(ldb_exclusive_scan_u32(ctx, chunk_cnt, chunk_off, n_chunks, d_sorted_groups));
+      LDB_TRY(ldb_read_u64(ctx, d_sorted_groups, &sorted_groups));
+      dh_desc.release();
+      sorted_tmp.free(chunk_cnt);
+      h->dense_sorted = 1;
+      h->ordered_slots = 0;
+      h->chunk_off = (uint64_t) chunk_off;
+      g.cap = std::max<uint64_t>(1, sorted_groups); // the dense group array: exactly one slot per group
+      sorted_chunks = (uint64_t) n_chunks;
+      // groups inside one wave leave the kernel as final rows; the table shrinks to one slot per CHUNK for the groups that cross a
+      // chunk boundary (DGroupBy::dense_out)
+      h->dense_out = ldb_option("gb_dense_out", 1) != 0 ? 1 : 0;
+      if (h->dense_out) g.cap = std::max<uint64_t>(1, sorted_chunks);
+      // … and the key column itself: the first row of a group has its key in a register (no representative rows + gather afterwards: Q18's
+      // 150 M keys, k_gather 0.72 ms); representative rows are still written when an ANY aggregate reads them
+      if (h->dense_out && ldb_option("gb_dense_keys", 1) != 0 && !kc.validity && (kc.width == 4 || kc.width == 8 || kc.width == 16) && kc.type.type != LDB_T_UTF8 &&
+          h->keys.cols[0].width == kc.width) {
+         h->dense_keys = any_fn() ? 1 : 2;
+         h->direct_key_width = kc.width;
+         direct_src = &kc;
+      }
+      return LDB_OK;
+   }
+   // the global table's slot scheme for ONE integer key that LDS cannot pre-aggregate: ordered by key, dense over a sorted column, or addressed
+   // directly by key - kmin; everything else keeps hashed slots
+   int32_t choose_layout() {
+      if (h->use_lds || n_keys != 1 || in->n_rows <= 0) return LDB_OK;
+      const ldb_rel_side& ks = in->sides[(size_t) keys[0].side];
+      const ldb_column& kc = ks.table->cols[(size_t) keys[0].col];
+      // ordered global slots (DGroupBy::ordered_slots): a 32-bit value range
+      if (ldb_option("gb_ordered", 1) != 0) {
+         int64_t lo = 0, hi = -1;
+         if (!kc.skewed && ldb_column_range(ctx, ks.table, keys[0].col, &lo, &hi) == LDB_OK && hi >= lo && (unsigned __int128) ((__int128) hi - lo) < ((unsigned __int128) 1 << 32)) {
+            h->ordered_slots = 1;
+            h->kmin = lo;
+            key_range = (unsigned __int128) ((__int128) hi - lo) + 1;
+         }
+      }
+      if (ldb_option("gb_sorted", 1) != 0 && h->n_preds == 0) {
+         bool sorted = false;
+         if (!ks.rowids) LDB_TRY(ldb_column_sorted(ctx, ks.table, keys[0].col, &sorted));
+         if (sorted) LDB_TRY(sorted_layout(kc));
+      }
+      // direct-address slots (DGroupBy::direct): a NOT NULL key whose value range is at most twice the expected number of groups
+      if (ldb_option("gb_direct", 1) != 0 && h->ordered_slots && !h->dense_sorted) {
+         const uint64_t expect = std::max<uint64_t>(g.est ? g.est : (uint64_t) in->n_rows, 1024);
+         if (!any_fn() && !kc.validity && !(ks.rowids && ks.may_null) && (kc.width == 4 || kc.width == 8 || kc.width == 16) && key_range <= (unsigned __int128) expect * 2 &&
+             key_range <= ((unsigned __int128) 1 << 30)) {
+            int32_t idx;
+            LDB_TRY(b.add_rows_counter(&idx)); // (an existing COUNT(*) accumulator is reused)
+            h->direct = 1;
+            h->direct_word = h->accs[idx].word;
+            h->direct_key_width = kc.width;
+            direct_src = &kc;
+            g.cap = std::max<uint64_t>(1024, next_pow2_u64((uint64_t) key_range));
+         }
+      }
+      return LDB_OK;
+   }
+
+   int32_t attempt_alloc(GbAttempt& at) {
+      const uint64_t cap = g.cap;
+      h->g_cap = cap;
+      h->kmult = h->ordered_slots ? (uint64_t) ((((unsigned __int128) cap) << 32) / key_range) : 0;
+      uint8_t* cross = nullptr;
+      if (!h->dense_out) LDB_TRY(at.table.alloc(&at.gk, 8 * (size_t) cap));
+      LDB_TRY(at.table.alloc(&at.ga, 8 * (size_t) cap * (size_t) h->n_words));
+      h->g_keys = (uint64_t) at.gk;
+      h->g_acc = (uint64_t) at.ga;
+      LDB_TRY(ldb_counters(ctx, 2 + GB_MAX_OUT, (uint64_t**) &at.d_ctl));
+      h->g_flags = (uint64_t) at.d_ctl;
+      const uint64_t max_groups = at.max_groups = std::max<uint64_t>(1, h->keyless ? 1 : h->dense_sorted ? sorted_groups : std::min<uint64_t>(cap, (uint64_t) in->n_rows));
+      h->dense_groups = h->dense_sorted ? max_groups : 0;
+      if (h->dense_out) {
+         LDB_TRY(at.table.alloc(&cross, (size_t) sorted_chunks + 8));
+         LDB_HIP(hipMemsetAsync(cross, 0, (size_t) sorted_chunks + 8, ctx->stream));
+         h->cross_flags = (uint64_t) cross;
+      }
+      if (h->direct || h->dense_keys) {
+         LDB_TRY(outs.alloc(&direct_keys, (size_t) h->direct_key_width * (size_t) max_groups));
+         h->direct_keys_out = (uint64_t) direct_keys;
+      }
+      if (!h->direct && h->dense_keys != 2) {
+         LDB_TRY(outs.alloc(&rep_rows, 4 * (size_t) max_groups));
+         h->rep_rows_out = (uint64_t) rep_rows;
+         // ordered slots give up on long probe runs, which depends on the insertion order: should a REPLAYED execution
+         // (ldb_readback) meet that where the recorded one did not, its group count is too high until the trace ends and the
+         // execution is repeated — the representative rows beyond the real count must then still be valid row numbers
+         if (h->ordered_slots && ctx->trace_mode == 2) LDB_HIP(hipMemsetAsync(rep_rows, 0, 4 * (size_t) max_groups, ctx->stream));
+      }
+      for (int32_t a = 0; a < n_aggs; a++) {
+         LDB_TRY(outs.alloc(&out_vals[(size_t) a], (size_t) h->outs[a].out_width * (size_t) max_groups));
+         h->outs[a].out_values = (uint64_t) out_vals[(size_t) a];
+         h->outs[a].out_valid = 0;
+         if (h->outs[a].cnt_acc >= 0 || h->outs[a].cnt_rows_acc >= 0 || h->outs[a].fn == LDB_AGG_ANY) {
+            LDB_TRY(outs.alloc(&out_valid[(size_t) a], (size_t) max_groups));
+            LDB_TRY(outs.alloc(&bitmaps[(size_t) a], (size_t) ((max_groups + 7) / 8 + 1)));
+            h->outs[a].out_valid = (uint64_t) out_valid[(size_t) a];
+         }
+      }
+      return LDB_OK;
+   }
+
+   // ---- the four aggregation strategies
+   // the rows' direct slots (+ their row numbers when `prow`) through the write-combining two-pass partition (ldb_wc.hip): written once as a dense
+   // array, tile-sorted by partition in LDS and stored in full-line runs
+   int32_t wc_partition(GbAttempt& at, LdbBufs& tmpb, uint32_t shift, uint32_t** slots, uint32_t** prow, uint32_t** part, uint32_t* chunks) {
+      const int64_t n_rows = in->n_rows;
+      uint32_t* raw;
+      LDB_TRY(tmpb.alloc(&raw, 4 * (size_t) n_rows));
+      LDB_TRY(tmpb.alloc(slots, 4 * (size_t) n_rows));
+      if (prow) LDB_TRY(tmpb.alloc(prow, 4 * (size_t) n_rows));
+      {
+         LdbProf prof_(ctx, "k_gbp_slots");
+         hipLaunchKernelGGL(k_gbp_slots, dim3(ldb_grid_for(ctx, n_rows, 256, 8)), dim3(256), 0, ctx->stream, (const DGroupBy*) at.desc.p, raw);
+      }
+      LDB_TRY(ldb_wc_partition(ctx, raw, nullptr, (uint64_t) n_rows, 0u, (uint32_t) (g.cap - 1), shift, (uint32_t) (g.cap >> shift), *slots, prow ? *prow : nullptr, part, chunks,
+                               "k_gbp_hist", "k_gbp_scatter"));
+      tmpb.adopt(*part);
+      return LDB_OK;
+   }
+   // COUNT(*) per key over direct slots, partitioned with write-combining — the one-pass scatter below keeps nparts open 4-byte streams per
+   // workgroup (Q13: 1 024), most of whose lines leave the L2 half written (2.4 ms for 148 M rows)
+   int32_t count_partitioned_wc(GbAttempt& at, uint32_t nparts) {
+      LdbBufs tmpb(ctx);
+      uint32_t *slots, *part = nullptr, chunks = 1;
+      LDB_TRY(wc_partition(at, tmpb, GBP_SHIFT, &slots, nullptr, &part, &chunks));
+      LdbProf prof_(ctx, "k_gbp_count");
+      hipLaunchKernelGGL(k_gbp_count, dim3(nparts), dim3(GBP_BLOCK), 0, ctx->stream, (const uint32_t*) slots, (const uint32_t*) part, chunks, nparts, (uint64_t) in->n_rows,
+                         at.ga + (uint64_t) h->direct_word * g.cap);
+      return LDB_OK;
+   }
+   // the same with the one-pass scatter: histogram, scan, scatter with workgroup-private cursors
+   int32_t count_partitioned_scatter(GbAttempt& at, uint32_t nparts) {
+      const int64_t n_rows = in->n_rows;
+      const DGroupBy* d = at.desc.p;
+      const uint32_t g0 = (uint32_t) std::max<int64_t>(1, std::min<int64_t>((int64_t) ctx->cus, (n_rows + 16383) / 16384));
+      const uint64_t rows_per_wg = ((uint64_t) n_rows + g0 - 1) / g0;
+      const size_t hn = (size_t) nparts * g0;
+      LdbBufs tmpb(ctx);
+      uint32_t *hist, *offs, *slots;
+      LDB_TRY(tmpb.alloc(&hist, 4 * hn));
+      LDB_TRY(tmpb.alloc(&offs, 4 * hn));
+      LDB_TRY(tmpb.alloc(&slots, 4 * (size_t) n_rows));
+      {
+         LdbProf prof_(ctx, "k_gbp_hist");
+         hipLaunchKernelGGL(k_gbp_hist, dim3(g0), dim3(GBP_SBLOCK), 0, ctx->stream, d, nparts, rows_per_wg, hist);
+      }
+      LDB_TRY(ldb_exclusive_scan_u32(ctx, hist, offs, (int64_t) hn, nullptr));
+      {
+         LdbProf prof_(ctx, "k_gbp_scatter");
+         hipLaunchKernelGGL(k_gbp_scatter, dim3(g0), dim3(GBP_SBLOCK), 0, ctx->stream, d, nparts, rows_per_wg, (const uint32_t*) offs, slots);
+      }
+      LdbProf prof_(ctx, "k_gbp_count");
+      hipLaunchKernelGGL(k_gbp_count, dim3(nparts), dim3(GBP_BLOCK), 0, ctx->stream, (const uint32_t*) slots, (const uint32_t*) offs, g0, nparts, (uint64_t) n_rows,
+                         at.ga + (uint64_t) h->direct_word * g.cap);
+      return LDB_OK;
+   }
+   // any aggregates over direct slots too many for the caches, many rows: partition (slot, row) pairs, aggregate every slot range in LDS
+   int32_t aggregate_partitioned(GbAttempt& at, uint32_t pv_shift) {
+      LdbBufs tmpb(ctx);
+      uint32_t *slots, *prow, *part = nullptr, chunks = 1;
+      LDB_TRY(wc_partition(at, tmpb, pv_shift, &slots, &prow, &part, &chunks));
+      LdbProf prof_(ctx, "k_gbp_agg");
+      hipLaunchKernelGGL(k_gbp_agg, dim3((uint32_t) (g.cap >> pv_shift)), dim3(GBP_BLOCK), (size_t) 8 * (size_t) h->n_words << pv_shift, ctx->stream, (const DGroupBy*) at.desc.p,
+                         (const uint32_t*) slots, (const uint32_t*) prow, (const uint32_t*) part, chunks, (uint32_t) (g.cap >> pv_shift), (uint64_t) in->n_rows, pv_shift);
+      return LDB_OK;
+   }
+   // the fused scan + aggregation kernel, generic or specialised
+   int32_t aggregate_plain(GbAttempt& at) {
+      const DGroupBy* d = at.desc.p;
+      int per_cu = g.lds_bytes > 40 * 1024 ? 2 : 4;
+      // (the sorted, LDS-free path was swept over 2 / 3 / 4 / 6 / 8 resident workgroups per CU: 5.52 / 4.22 / 3.90 / 3.70 / 3.83 ms on one box, but 6 gave 4.05 ms on the
+      // next one where 4 gives ≈ 3.95: inside the box-to-box spread, so the default stays)
+      if (const int64_t forced = ldb_option("gb_wgs_per_cu", 0)) per_cu = (int) std::max<int64_t>(1, std::min<int64_t>(forced, 16)); // experiments (Q1's line re-fetches)
+      const int grid = ldb_grid_for(ctx, in->n_rows, GB_BLOCK, per_cu);
+      hipFunction_t spec = nullptr;
+      if (ldb_jit_wanted(in->n_rows)) {
+         std::string why;
+         spec = ldb_jit_groupby(ctx->device, h, &why);
+         if (!spec) ldb_set_error("groupby: specialised kernel unavailable (%s); using the generic kernel", why.c_str());
+      }
+      LdbProf prof_(ctx, h->direct ? "k_groupby_direct" : "k_groupby"); // (the same kernel; the name tells the profile which slot scheme ran)
+      if (spec) {
+         void* params[] = {(void*) &d};
+         LDB_HIP(hipModuleLaunchKernel(spec, (unsigned) grid, 1, 1, GB_BLOCK, 1, 1, (unsigned) g.lds_bytes, ctx->stream, params, nullptr));
+      } else {
+         hipLaunchKernelGGL(k_groupby, dim3(grid), dim3(GB_BLOCK), g.lds_bytes, ctx->stream, d);
+      }
+      return LDB_OK;
+   }
+   int32_t launch_aggregate(GbAttempt& at) {
+      const int64_t n_rows = in->n_rows;
+      const bool many_rows = n_rows >= ldb_option("gb_partition_min_rows", 8ll << 20) && (uint64_t) n_rows < (1ull << 32) && ldb_option("gb_partition", 1) != 0;
+      // COUNT(*) per key over direct slots, many rows into a table far beyond the L2: partition, then count in LDS
+      const bool partitioned = h->direct && h->n_words == 1 && h->n_accs == 1 && h->n_preds == 0 && h->n_cpreds == 0 && g.cap >= (1ull << 20) && (g.cap >> GBP_SHIFT) <= GBP_MAX_PARTS && many_rows;
+      // the same for arbitrary aggregates (k_gbp_agg): as many slots per partition as their accumulator words fit into 60 KB of LDS
+      uint32_t pv_shift = 0;
+      while (pv_shift < 16 && ((size_t) 8 * (size_t) h->n_words << (pv_shift + 1)) <= 60 * 1024) pv_shift++;
+      bool wide_minmax = false;
+      for (int a = 0; a < h->n_accs; a++) wide_minmax = wide_minmax || h->accs[a].kind == ACC_MIN128 || h->accs[a].kind == ACC_MAX128;
+      const bool part_values = !partitioned && h->direct && h->n_preds == 0 && !wide_minmax && g.cap >= (1ull << 20) && pv_shift >= 8 && (g.cap >> pv_shift) <= GBP_MAX_PARTS && many_rows &&
+         ldb_option("gb_partition_values", 1) != 0;
+      if (partitioned) {
+         const uint32_t nparts = (uint32_t) (g.cap >> GBP_SHIFT);
+         if (ldb_option("gb_partition_wc", 1) != 0 && nparts > 64) LDB_TRY(count_partitioned_wc(at, nparts));
+         else LDB_TRY(count_partitioned_scatter(at, nparts));
+      } else if (part_values) {
+         LDB_TRY(aggregate_partitioned(at, pv_shift));
+      } else if (n_rows) {
+         LDB_TRY(aggregate_plain(at));
+      }
+      LDB_HIP(hipGetLastError());
+      return LDB_OK;
+   }
+
+   // ---- finalize (speculative: queued right behind the aggregation without waiting for its flags; valid only if they come back clean)
+   // per-group validity bytes → Arrow bitmaps + NULL counts; d_count = the device word that holds the number of groups
+   void pack_valid(GbAttempt& at, const unsigned long long* d_count) {
+      for (int32_t a = 0; a < n_aggs; a++)
+         if (out_valid[(size_t) a])
+            hipLaunchKernelGGL(k_pack_valid_bytes, dim3(ldb_grid_for(ctx, (int64_t) at.max_groups, 256 * 8, 4)), dim3(256), 0, ctx->stream, out_valid[(size_t) a], bitmaps[(size_t) a], d_count,
+                               (uint64_t) at.max_groups, at.d_ctl + 2 + a);
+   }
+   // dense_out: every group inside one wave is final already — only the chunk-crossing groups are left, the count is known
+   int32_t finalize_dense(GbAttempt& at) {
+      LdbProf prof_(ctx, "k_gb_finalize");
+      hipLaunchKernelGGL(k_gb_finalize_cross, dim3(ldb_grid_for(ctx, (int64_t) sorted_chunks, 256, 8)), dim3(256), 0, ctx->stream, (const DGroupBy*) at.desc.p, sorted_chunks,
+                         (const unsigned long long*) d_sorted_groups);
+      pack_valid(at, (const unsigned long long*) d_sorted_groups);
+      LDB_HIP(hipGetLastError());
+      return LDB_OK;
+   }
+   // occupied slots per 64-slot chunk → exclusive scan (the group count lands in ctl[1]) → k_gb_finalize compacts the groups
+   int32_t finalize_slots(GbAttempt& at) {
+      const uint64_t cap = g.cap;
+      LdbProf prof_(ctx, "k_gb_finalize");
+      const int64_t n_chunks = (int64_t) ((cap + 63) / 64);
+      LdbBufs fin(ctx);
+      uint32_t *pop = nullptr, *off;
+      LDB_TRY(fin.alloc(&off, 4 * (size_t) n_chunks));
+      const int fgrid = ldb_grid_for(ctx, (int64_t) cap, 256, 8);
+      const uint64_t* occ = h->direct ? (const uint64_t*) h->g_acc + (uint64_t) h->direct_word * cap : (const uint64_t*) h->g_keys;
+      if (ldb_option("scan_single_pass", 1) != 0) { // occupied slots per chunk + their exclusive scan + the group count: one chained launch
+         const uint64_t n_tiles = ((uint64_t) n_chunks + GBO_TILE_CHUNKS - 1) / GBO_TILE_CHUNKS;
+         ChainCall c;
+         LDB_TRY(ldb_chain_begin(ctx, n_tiles, false, &c));
+         hipLaunchKernelGGL(k_gb_occupancy_scan, dim3((unsigned) n_tiles), dim3(256), 0, ctx->stream, occ, cap, (uint64_t) n_chunks, n_tiles, off, at.d_ctl + 1, c.status, c.ticket, c.ticket_base,
+                            c.epoch);
+         if (hipGetLastError() != hipSuccess) return ldb_chain_failed(ctx);
+      } else {
+         LDB_TRY(fin.alloc(&pop, 4 * (size_t) n_chunks));
+         hipLaunchKernelGGL(k_gb_occupancy, dim3(fgrid), dim3(256), 0, ctx->stream, occ, cap, pop);
+         LDB_TRY(ldb_exclusive_scan_u32(ctx, pop, off, n_chunks, (uint64_t*) (at.d_ctl + 1)));
+      }
+      hipLaunchKernelGGL(k_gb_finalize, dim3(fgrid), dim3(256), 0, ctx->stream, (const DGroupBy*) at.desc.p, rep_rows, (const uint32_t*) off);
+      pack_valid(at, at.d_ctl + 1);
+      LDB_HIP(hipGetLastError());
+      return LDB_OK;
+   }
+   int32_t verdict(GbVerdict* v) {
+      const uint64_t flags = (uint64_t) ctl[0];
+      *v = GB_DONE;
+      if ((flags & 3) == 0) return LDB_OK;
+      outs.free_all();
+      forget_outputs();
+      if ((flags & 2) && h->ordered_slots) { // long probe runs: this key distribution needs hashed slots
+         h->ordered_slots = 0;
+         in->sides[(size_t) keys[0].side].table->cols[(size_t) keys[0].col].skewed = true;
+         *v = GB_RETRY_HASHED;
+         if ((flags & 1) == 0) return LDB_OK;
+      }
+      // global table overflowed: retry larger (the estimate was too low)
+      if (g.cap >= g.cap_max) LDB_FAIL(LDB_ERR_HIP, "groupby: global table overflow at maximum capacity");
+      g.cap = std::min(g.cap * 8, g.cap_max);
+      *v = GB_RETRY_LARGER;
+      return LDB_OK;
+   }
+   int32_t attempt(GbVerdict* v) {
+      GbAttempt at(ctx);
+      LDB_TRY(attempt_alloc(at));
+      LDB_TRY(at.desc.upload(h, sizeof(*h)));
+      hipLaunchKernelGGL(k_gb_init, dim3(ldb_grid_for(ctx, (int64_t) g.cap, 256, 8)), dim3(256), 0, ctx->stream, at.gk, at.ga, (const DGroupBy*) at.desc.p);
+      LDB_TRY(launch_aggregate(at));
+      LDB_TRY(h->dense_out ? finalize_dense(at) : finalize_slots(at));
+      static_assert(sizeof(ctl) <= 64 * sizeof(int64_t), "control block must fit the pinned scratch words");
+      LDB_TRY(LDB_READBACK(ctx, ctl, at.d_ctl, sizeof(ctl)));
+      if (h->dense_out) ctl[1] = sorted_groups; // (no occupancy scan ran: the heads pass counted the groups)
+      at.desc.release();
+      return verdict(v);
+   }
+
+   // key columns = gather of the representative rows (or what the kernels wrote themselves), then the aggregates
+   int32_t result_table(ldb_table** out) {
+      const uint64_t n_groups = (uint64_t) ctl[1];
+      LdbTableHold res(ctx, new ldb_table());
+      res->ctx = ctx;
+      res->name = "groupby";
+      res->n_rows = (int64_t) n_groups;
+      res->cols.resize((size_t) (n_keys + n_aggs));
+      if (h->direct || h->dense_keys) { // the key column was written by k_gb_finalize / by the sorted aggregation itself
+         ldb_column& kc = res->cols[0];
+         kc.name = direct_src->name;
+         kc.type = direct_src->type;
+         kc.width = direct_src->width;
+         kc.values = direct_keys;
+         outs.keep(direct_keys);
+         kc.value_bytes = (int64_t) n_groups * kc.width;
+         kc.owned = true;
+         if (direct_src->has_range) { // the groups' keys are values of the source column: its cached range stays a valid superset
+            kc.has_range = true;
+            kc.vmin = direct_src->vmin;
+            kc.vmax = direct_src->vmax;
+         }
+         outs.free(rep_rows); // (sorted keys with an ANY aggregate: the representative rows were only read by the finalisation)
+      } else {
+         LdbRelHold reps(ctx);
+         outs.keep(rep_rows); // (ldb_rel_select takes the selection over)
+         LDB_TRY(ldb_rel_select(ctx, in, rep_rows, (int64_t) n_groups, &reps.r));
+         if (n_keys) LDB_TRY(ldb_gather_columns(ctx, reps.r, keys, n_keys, res->cols.data()));
+      }
+      for (int32_t a = 0; a < n_aggs; a++) {
+         ldb_column& c = res->cols[(size_t) (n_keys + a)];
+         char nm[32];
+         snprintf(nm, sizeof(nm), "agg%d", a);
+         c.name = nm;
+         c.type = otypes[(size_t) a];
+         c.width = h->outs[a].out_width;
+         c.values = out_vals[(size_t) a];
+         outs.keep(c.values);
+         c.value_bytes = (int64_t) n_groups * c.width;
+         c.owned = true;
+         if (is_str[(size_t) a]) { // a LAZY utf8 column (ldb_column_is_lazy): the codes the kernels wrote + the argument column's dictionary
+            const ldb_column& sc = in->sides[(size_t) str_ref[(size_t) a].side].table->cols[(size_t) str_ref[(size_t) a].col];
+            c.type = sc.type;
+            c.type.nullable = 1;
+            c.width = sc.width;
+            c.dict_codes = (uint32_t*) c.values;
+            c.values = nullptr;
+            c.value_bytes = -1;
+            c.dict = sc.dict;
+            c.dict->dict_refs++;
+            c.dict_size = sc.dict_size;
+            c.dict_pred_cache = new std::unordered_map<std::string, std::string>();
+         }
+         if (bitmaps[(size_t) a]) { // drop the bitmap when nothing is NULL
+            const int64_t nulls = (int64_t) ctl[2 + a];
+            if (nulls) {
+               c.validity = bitmaps[(size_t) a];
+               outs.keep(c.validity);
+               c.null_count = nulls;
+            } else {
+               outs.free(bitmaps[(size_t) a]);
+            }
+         }
+      }
+      LDB_HIP(hipGetLastError());
+      *out = res.release();
+      return LDB_OK;
+   }
+};
+
 extern "C" int32_t ldb_gpu_groupby(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_desc* preds, int32_t n_preds, const ldb_colref* keys, int32_t n_keys,
                                    const ldb_agg_spec* aggs, int32_t n_aggs, int64_t est_groups, ldb_table** out) {
    if (!ctx || !in || !out) LDB_FAIL(LDB_ERR_INVALID, "groupby: NULL argument");
@@ -474,7 +1083,7 @@ extern "C" int32_t ldb_gpu_groupby(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_d
             break;
          }
    // one integer key over a range too large for the caches, many rows, a lazy filter in front: the filter is evaluated FIRST — the partitioned
-   // aggregation below (k_gbp_agg) wants the surviving rows as a dense list, and a selective filter (Q15: 23 M of 600 M rows) then decides
+   // aggregation (k_gbp_agg) wants the surviving rows as a dense list, and a selective filter (Q15: 23 M of 600 M rows) then decides
    // whether it is worth it at all.  The fused alternative pays one global atomic per accumulator and surviving row.
    if (n_keys == 1 && n_preds == 0 && !in->pending.empty() && in->n_rows >= ldb_option("gb_partition_min_rows", 8ll << 20) && ldb_option("gb_partition", 1) != 0 &&
        ldb_option("gb_partition_values", 1) != 0 && ldb_option("gb_direct", 1) != 0 && est_groups >= (1 << 19)) {
@@ -495,615 +1104,19 @@ extern "C" int32_t ldb_gpu_groupby(ldb_ctx* ctx, ldb_rel* in, const ldb_filter_d
    h->n_preds = n_preds;
    for (int32_t p = 0; p < n_preds; p++) LDB_TRY(ldb_make_dpred(in, &preds[p], &h->preds[p]));
    for (auto& dp : in->pending) h->preds[h->n_preds++] = dp;
-   n_preds = h->n_preds;
-   ldb_order_preds(h->preds, n_preds); // cheap conjuncts first, same-column neighbours marked
-   h->batch_rows = n_preds >= 2 ? 8 : 4;
+   ldb_order_preds(h->preds, h->n_preds); // cheap conjuncts first, same-column neighbours marked
+   h->batch_rows = h->n_preds >= 2 ? 8 : 4;
    LDB_TRY(ldb_make_dkeys_dict(in, keys, n_keys, &h->keys)); // (dictionary codes stand in for low-cardinality strings: hashing and equality only)
    h->keyless = n_keys == 0;
-   GbBuilder b{in, h, {}};
 
-   auto add_acc = [&](DAcc& a, int words, uint64_t init, int32_t* idx) -> int32_t {
-      for (int k = 0; k < h->n_accs; k++)
-         if (same_acc(h->accs[k], a)) {
-            *idx = k;
-            return LDB_OK;
-         }
-      if (h->n_accs >= GB_MAX_ACCS || h->n_words + words > GB_MAX_WORDS) LDB_FAIL(LDB_ERR_UNSUPPORTED, "groupby: too many distinct accumulators");
-      a.word = h->n_words;
-      h->word_init[h->n_words] = init;
-      for (int k = 1; k < words; k++) h->word_init[h->n_words + k] = 0;
-      h->n_words += words;
-      h->accs[h->n_accs] = a;
-      *idx = h->n_accs++;
-      return LDB_OK;
-   };
-
-   // output table layout: keys then aggregates
-   LdbTableHold res(ctx, new ldb_table());
-   res->ctx = ctx;
-   res->name = "groupby";
-   h->n_outs = n_aggs;
-   struct OutInfo {
-      ldb_coltype type;
-      int width;
-   };
-   std::vector<OutInfo> oinfo((size_t) n_aggs);
-   for (int32_t a = 0; a < n_aggs; a++) {
-      const ldb_agg_spec& sp = aggs[a];
-      DOut& o = h->outs[a];
-      memset(&o, 0, sizeof(o));
-      o.fn = sp.fn;
-      o.wide = sp.wide;
-      o.avg_pow10 = sp.avg_pow10;
-      o.acc = -1;
-      o.cnt_acc = -1;
-      o.cnt_rows_acc = -1;
-      o.cnt_pass_acc = -1;
-      o.is_float = sp.arg.is_float && sp.fn != LDB_AGG_COUNT && sp.fn != LDB_AGG_COUNT_STAR;
-      if (sp.n_preds < 0 || sp.n_preds > LDB_MAX_AGG_PREDS) LDB_FAIL(LDB_ERR_INVALID, "groupby: aggregate %d has %d predicates", a, sp.n_preds);
-      if (sp.avg_pow10 < 0 || sp.avg_pow10 > 38) LDB_FAIL(LDB_ERR_INVALID, "groupby: avg_pow10 %d", sp.avg_pow10);
-      DAcc acc;
-      memset(&acc, 0, sizeof(acc));
-      acc.n_cpreds = sp.n_preds;
-      for (int p = 0; p < sp.n_preds; p++) {
-         DPred dp;
-         LDB_TRY(ldb_make_dpred(in, &sp.preds[p], &dp));
-         int found = -1;
-         for (int k = 0; k < h->n_cpreds; k++)
-            if (!memcmp(&h->cpreds[k], &dp, sizeof(DPred))) found = k;
-         if (found < 0) {
-            if (h->n_cpreds >= GB_MAX_CPREDS) LDB_FAIL(LDB_ERR_UNSUPPORTED, "groupby: too many conditional-aggregate predicates");
-            h->cpreds[h->n_cpreds] = dp;
-            found = h->n_cpreds++;
-         }
-         acc.cpred[p] = found;
-      }
-      bool nullable = false;
-      const bool str = is_str[(size_t) a];
-      if (str) { // grouped: only a dictionary makes a string a fixed-width value (an arg-min accumulator in every layout is the follow-up)
-         const ldb_colref sr = str_ref[(size_t) a];
-         if (sr.col < 0 || (size_t) sr.col >= in->sides[(size_t) sr.side].table->cols.size()) LDB_FAIL(LDB_ERR_INVALID, "groupby: aggregate %d: column %d:%d out of range", a, sr.side, sr.col);
-         const ldb_column& sc = in->sides[(size_t) sr.side].table->cols[(size_t) sr.col];
-         if (!sc.dict_codes || !sc.dict) LDB_FAIL(LDB_ERR_UNSUPPORTED, "groupby: grouped MIN / MAX over a string column without a dictionary");
-         o.wide = 0;
-      }
-      b.str_codes = str;
-      if (sp.fn != LDB_AGG_COUNT_STAR) LDB_TRY(b.conv_expr(&sp.arg, &acc.e, &nullable));
-      b.str_codes = false;
-      o.e = acc.e;
-      // counter of contributing rows: AVG divisor, and NULL-ness of SUM/MIN/MAX results
-      auto need_counter = [&](int32_t* idx) -> int32_t {
-         DAcc c = acc;
-         if (sp.fn == LDB_AGG_AVG && sp.has_count_expr) {
-            // merging partial (sum, count) states: the divisor is SUM(count_expr)
-            bool cn = false;
-            c.kind = ACC_SUM64;
-            c.count_rows = 0;
-            LDB_TRY(b.conv_expr(&sp.count_expr, &c.e, &cn));
-            if (c.e.is_float) LDB_FAIL(LDB_ERR_INVALID, "groupby: AVG count_expr must be an integer expression");
-            return add_acc(c, 1, 0, idx);
-         }
-         c.kind = ACC_COUNT;
-         c.count_rows = (!nullable && sp.fn != LDB_AGG_COUNT) ? 1 : 0;
-         if (c.count_rows) memset(&c.e, 0, sizeof(c.e));
-         return add_acc(c, 1, 0, idx);
-      };
-      switch (sp.fn) {
-         case LDB_AGG_COUNT_STAR: {
-            acc.kind = ACC_COUNT;
-            acc.count_rows = 1;
-            LDB_TRY(add_acc(acc, 1, 0, &o.acc));
-            break;
-         }
-         case LDB_AGG_COUNT: {
-            acc.kind = ACC_COUNT;
-            acc.count_rows = nullable ? 0 : 1;
-            if (acc.count_rows) memset(&acc.e, 0, sizeof(acc.e));
-            LDB_TRY(add_acc(acc, 1, 0, &o.acc));
-            break;
-         }
-         case LDB_AGG_SUM:
-         case LDB_AGG_AVG: {
-            if (sp.arg.is_float) {
-               acc.kind = ACC_SUMF64;
-               LDB_TRY(add_acc(acc, 1, 0, &o.acc));
-            } else if (sp.wide) {
-               acc.kind = ACC_SUM128;
-               LDB_TRY(add_acc(acc, 2, 0, &o.acc));
-            } else {
-               acc.kind = ACC_SUM64;
-               LDB_TRY(add_acc(acc, 1, 0, &o.acc));
-            }
-            // a plain SUM over no non-NULL input is NULL; a conditional SUM (case … else 0) gets a
-            // non-NULL 0 from every row failing its predicates (see DOut::cnt_rows_acc)
-            if (sp.fn == LDB_AGG_AVG || nullable || (h->keyless && sp.n_preds == 0)) LDB_TRY(need_counter(&o.cnt_acc));
-            if (sp.fn == LDB_AGG_SUM && sp.n_preds > 0 && (nullable || h->keyless)) {
-               DAcc rows;
-               memset(&rows, 0, sizeof(rows));
-               rows.kind = ACC_COUNT;
-               rows.count_rows = 1;
-               LDB_TRY(add_acc(rows, 1, 0, &o.cnt_rows_acc));
-               if (nullable) {
-                  DAcc passing = acc; // same predicates, counts rows
-                  passing.kind = ACC_COUNT;
-                  passing.count_rows = 1;
-                  memset(&passing.e, 0, sizeof(passing.e));
-                  LDB_TRY(add_acc(passing, 1, 0, &o.cnt_pass_acc));
-               }
-            }
-            break;
-         }
-         case LDB_AGG_MIN:
-         case LDB_AGG_MAX: {
-            if (sp.wide && !sp.arg.is_float && !str) { // low word, signed high word, lock word (d_sink_minmax128)
-               acc.kind = sp.fn == LDB_AGG_MIN ? ACC_MIN128 : ACC_MAX128;
-               LDB_TRY(add_acc(acc, 3, 0, &o.acc));
-               const int w0 = h->accs[o.acc].word;
-               h->word_init[w0] = sp.fn == LDB_AGG_MIN ? ~0ull : 0ull;
-               h->word_init[w0 + 1] = sp.fn == LDB_AGG_MIN ? (uint64_t) INT64_MAX : (uint64_t) INT64_MIN;
-               h->word_init[w0 + 2] = 0;
-            } else if (sp.arg.is_float) {
-               double init = sp.fn == LDB_AGG_MIN ? __builtin_inf() : -__builtin_inf();
-               uint64_t bits;
-               memcpy(&bits, &init, 8);
-               acc.kind = sp.fn == LDB_AGG_MIN ? ACC_MINF64 : ACC_MAXF64;
-               LDB_TRY(add_acc(acc, 1, bits, &o.acc));
-            } else {
-               acc.kind = sp.fn == LDB_AGG_MIN ? ACC_MIN64 : ACC_MAX64;
-               LDB_TRY(add_acc(acc, 1, sp.fn == LDB_AGG_MIN ? (uint64_t) INT64_MAX : (uint64_t) INT64_MIN, &o.acc));
-            }
-            if (nullable || h->keyless || sp.n_preds) LDB_TRY(need_counter(&o.cnt_acc));
-            break;
-         }
-         case LDB_AGG_ANY: // evaluated on the group's representative row
-            // the key-less group is pre-seeded with row 0 as its representative, which need not pass a fused filter
-            if (h->keyless && h->n_preds > 0) LDB_FAIL(LDB_ERR_UNSUPPORTED, "groupby: ANY in a key-less aggregation with fused predicates (filter the relation first)");
-            break;
-         default: LDB_FAIL(LDB_ERR_INVALID, "groupby: unknown aggregate function %d", sp.fn);
-      }
-      ldb_coltype ot{};
-      ot.type = sp.out_type;
-      ot.precision = sp.out_precision;
-      ot.scale = sp.out_scale;
-      ot.nullable = 1;
-      if (o.is_float) ot.type = LDB_T_FLOAT64;
-      if (sp.fn == LDB_AGG_COUNT || sp.fn == LDB_AGG_COUNT_STAR) ot.type = LDB_T_INT64;
-      if (str) ot.type = LDB_T_INT32; // the kernels write the winning code; the column becomes codes + the shared dictionary below
-      int w = ldb_width_of(ot, 0);
-      if (w != 4 && w != 8 && w != 16) LDB_FAIL(LDB_ERR_INVALID, "groupby: aggregate %d output type %d unsupported", a, ot.type);
-      o.out_width = w;
-      oinfo[(size_t) a] = {ot, w};
-   }
-   // at least one word so that every slot has something to initialise
-   if (h->n_words == 0) {
-      DAcc c;
-      memset(&c, 0, sizeof(c));
-      c.kind = ACC_COUNT;
-      c.count_rows = 1;
-      int32_t idx;
-      LDB_TRY(add_acc(c, 1, 0, &idx));
-   }
-
-   // ---- geometry
-   int nw = h->n_words;
-   const size_t slot_bytes = 8 * (size_t) (1 + nw);
-   const size_t lds_budget = 60 * 1024;
-   uint64_t est = est_groups > 0 ? (uint64_t) est_groups : 0;
-   if (h->keyless) est = 1;
-   uint32_t S, R;
-   h->use_lds = 1;
-   if (h->keyless) {
-      S = 1;
-      R = 64;
-   } else if (est == 0) {
-      S = 1;
-      while ((size_t) S * 2 * slot_bytes <= lds_budget && S < 4096) S <<= 1;
-      R = 1;
-   } else {
-      S = (uint32_t) std::max<uint64_t>(8, next_pow2_u64(est * 2));
-      if ((size_t) S * slot_bytes > lds_budget) {
-         // more groups than LDS can pre-aggregate: the hit rate of a small cache is poor when
-         // the input is not clustered, so go straight to the global table
-         uint32_t smax = 1;
-         while ((size_t) smax * 2 * slot_bytes <= lds_budget) smax <<= 1;
-         S = smax;
-         if (est > (uint64_t) smax * 4) h->use_lds = 0;
-         R = 1;
-      } else {
-         R = 1;
-         while (R < 64 && (size_t) S * (R * 2) * slot_bytes <= lds_budget) R <<= 1;
-      }
-   }
-   h->lds_slots = S;
-   h->lds_reps = R;
-   size_t lds_bytes = h->use_lds ? (size_t) S * R * slot_bytes : 0;
-
-   uint64_t cap_guess = est ? est * 2 : std::min<uint64_t>((uint64_t) in->n_rows * 2, 1ull << 22);
-   uint64_t cap = std::max<uint64_t>(1024, next_pow2_u64(cap_guess));
-   const uint64_t cap_max = next_pow2_u64(std::max<uint64_t>(1024, (uint64_t) in->n_rows * 2));
-   if (cap > cap_max) cap = cap_max;
-
-   // ordered global slots (DGroupBy::ordered_slots): one integer key with a 32-bit value range
-   unsigned __int128 key_range = 0;
-   const bool gb_ordered = ldb_option("gb_ordered", 1) != 0;
-   if (gb_ordered && !h->use_lds && n_keys == 1 && in->n_rows > 0) {
-      int64_t lo = 0, hi = -1;
-      const ldb_rel_side& ks = in->sides[(size_t) keys[0].side];
-      if (!ks.table->cols[(size_t) keys[0].col].skewed && ldb_column_range(ctx, ks.table, keys[0].col, &lo, &hi) == LDB_OK && hi >= lo &&
-          (unsigned __int128) ((__int128) hi - lo) < ((unsigned __int128) 1 << 32)) {
-         h->ordered_slots = 1;
-         h->kmin = lo;
-         key_range = (unsigned __int128) ((__int128) hi - lo) + 1;
-      }
-   }
-   // sorted key column, no filter (DGroupBy::dense_sorted): number the groups by key changes
-   void* direct_keys = nullptr; // the output key column where the kernel writes it itself (direct slots; sorted keys with dense_keys)
-   const ldb_column* direct_src = nullptr;
-   uint32_t* chunk_off = nullptr;
-   LdbBufs sorted_tmp(ctx); // the sorted path's chunk counts / offsets
-   uint64_t sorted_groups = 0, sorted_chunks = 0; // dense_sorted: number of groups / of 64-row chunks
-   uint64_t* d_sorted_groups = nullptr; // the same count on the device (an arena word)
-   const bool gb_sorted = ldb_option("gb_sorted", 1) != 0;
-   if (gb_sorted && !h->use_lds && n_keys == 1 && h->n_preds == 0 && in->n_rows > 0) {
-      const ldb_rel_side& ks = in->sides[(size_t) keys[0].side];
-      bool sorted = false;
-      if (!ks.rowids) LDB_TRY(ldb_column_sorted(ctx, ks.table, keys[0].col, &sorted));
-      if (sorted) {
-         const int64_t n_chunks = (in->n_rows + 63) / 64;
-         uint32_t* chunk_cnt;
-         LDB_TRY(sorted_tmp.alloc(&chunk_cnt, 4 * (size_t) n_chunks));
-         LDB_TRY(sorted_tmp.alloc(&chunk_off, 4 * (size_t) n_chunks));
-         LdbDesc<DGroupBy> dh_desc(ctx);
-         LDB_TRY(dh_desc.upload(h, sizeof(*h)));
-         DGroupBy* dh = dh_desc.p;
-         {
-            const int hgrid = ldb_grid_for(ctx, in->n_rows, 256, 8);
-            hipFunction_t spec = nullptr;
-            std::string why;
-            if (ldb_jit_wanted(in->n_rows)) spec = ldb_jit_groupby_kernel(ctx->device, h, "k_gb_sorted_heads_spec", &why);
-            LdbProf prof_(ctx, "k_gb_sorted_heads");
-            if (spec) {
-               void* params[] = {(void*) &dh, (void*) &chunk_cnt};
-               LDB_HIP(hipModuleLaunchKernel(spec, (unsigned) hgrid, 1, 1, 256, 1, 1, 0, ctx->stream, params, nullptr));
-            } else {
-               hipLaunchKernelGGL(k_gb_sorted_heads, dim3(hgrid), dim3(256), 0, ctx->stream, dh, chunk_cnt);
-            }
-         }
-         uint64_t* d_groups;
-         LDB_TRY(ldb_counters(ctx, 1, &d_groups));
-         LDB_TRY(ldb_exclusive_scan_u32(ctx, chunk_cnt, chunk_off, n_chunks, d_groups));
-         uint64_t groups = 0;
-         LDB_TRY(ldb_read_u64(ctx, d_groups, &groups));
-         dh_desc.release();
-         sorted_tmp.free(chunk_cnt);
-         h->dense_sorted = 1;
-         h->ordered_slots = 0;
-         h->chunk_off = (uint64_t) chunk_off;
-         cap = std::max<uint64_t>(1, groups); // the dense group array: exactly one slot per group
-         sorted_groups = groups;
-         sorted_chunks = (uint64_t) n_chunks;
-         d_sorted_groups = d_groups;
-         // groups inside one wave leave the kernel as final rows; the table shrinks to one slot per CHUNK for the groups that cross a
-         // chunk boundary (DGroupBy::dense_out)
-         h->dense_out = ldb_option("gb_dense_out", 1) != 0 ? 1 : 0;
-         if (h->dense_out) cap = std::max<uint64_t>(1, sorted_chunks);
-         // … and the key column itself: the first row of a group has its key in a register (no representative rows + gather afterwards: Q18's
-         // 150 M keys, k_gather 0.72 ms); representative rows are still written when an ANY aggregate reads them
-         const ldb_column& skc = ks.table->cols[(size_t) keys[0].col];
-         if (h->dense_out && ldb_option("gb_dense_keys", 1) != 0 && !skc.validity && (skc.width == 4 || skc.width == 8 || skc.width == 16) && skc.type.type != LDB_T_UTF8 &&
-             h->keys.cols[0].width == skc.width) {
-            bool any_fn = false;
-            for (int32_t a = 0; a < n_aggs; a++) any_fn = any_fn || aggs[a].fn == LDB_AGG_ANY;
-            h->dense_keys = any_fn ? 1 : 2;
-            h->direct_key_width = skc.width;
-            direct_src = &skc;
-         }
-      }
-   }
-   // direct-address slots (DGroupBy::direct): one NOT NULL integer key whose value range is at most twice
-   // the expected number of groups — the table is indexed by key - kmin
-   if (ldb_option("gb_direct", 1) != 0 && h->ordered_slots && !h->dense_sorted && n_keys == 1) {
-      const ldb_rel_side& ks = in->sides[(size_t) keys[0].side];
-      const ldb_column& kc = ks.table->cols[(size_t) keys[0].col];
-      bool any_fn = false;
-      for (int32_t a = 0; a < n_aggs; a++) any_fn = any_fn || aggs[a].fn == LDB_AGG_ANY;
-      const uint64_t expect = std::max<uint64_t>(est ? est : (uint64_t) in->n_rows, 1024);
-      if (!any_fn && !kc.validity && !(ks.rowids && ks.may_null) && (kc.width == 4 || kc.width == 8 || kc.width == 16) && key_range <= (unsigned __int128) expect * 2 &&
-          key_range <= ((unsigned __int128) 1 << 30)) {
-         DAcc rows;
-         memset(&rows, 0, sizeof(rows));
-         rows.kind = ACC_COUNT;
-         rows.count_rows = 1;
-         int32_t idx;
-         LDB_TRY(add_acc(rows, 1, 0, &idx)); // (an existing COUNT(*) accumulator is reused)
-         nw = h->n_words;
-         h->direct = 1;
-         h->direct_word = h->accs[idx].word;
-         h->direct_key_width = kc.width;
-         direct_src = &kc;
-         cap = std::max<uint64_t>(1024, next_pow2_u64((uint64_t) key_range));
-      }
-   }
-   // One control block per call, read back ONCE per attempt: [0] the kernel's overflow / long-probe
-   // flags, [1] the number of groups (total of the occupancy scan), [2 + a] NULLs of aggregate a.
-   // The finalisation (occupancy → scan → k_gb_finalize → validity packing) is queued right behind
-   // the aggregation kernel without waiting for its flags; an overflow (rare: the estimate was far
-   // too low) throws that work away and retries with a larger table.
-   const size_t ctl_bytes = 8 * (size_t) (2 + GB_MAX_OUT);
-   unsigned long long* d_ctl = nullptr; // zeroed arena words, fresh ones per attempt (ldb_counters)
-   unsigned long long ctl[2 + GB_MAX_OUT];
-   LdbDesc<DGroupBy> d_desc(ctx); // (one per attempt: given back after the attempt's control words are read, and on every error return)
-   DGroupBy* d = nullptr;
-   uint64_t n_groups = 0;
-   uint32_t* rep_rows = nullptr;
-   std::vector<void*> out_vals((size_t) n_aggs, nullptr);
-   std::vector<uint8_t*> out_valid((size_t) n_aggs, nullptr);
-   std::vector<uint8_t*> bitmaps((size_t) n_aggs, nullptr);
-   LdbBufs outs(ctx); // the output buffers: the survivors are kept into the result table, a failed attempt's are freed as a whole
-   for (;;) {
-      h->g_cap = cap;
-      h->kmult = h->ordered_slots ? (uint64_t) ((((unsigned __int128) cap) << 32) / key_range) : 0;
-      uint64_t *gk = nullptr, *ga;
-      uint8_t* cross = nullptr;
-      LdbBufs attempt(ctx); // the table of this attempt: released when the attempt ends, on every path (an error return included)
-      if (!h->dense_out) LDB_TRY(attempt.alloc(&gk, 8 * (size_t) cap));
-      LDB_TRY(attempt.alloc(&ga, 8 * (size_t) cap * (size_t) nw));
-      h->g_keys = (uint64_t) gk;
-      h->g_acc = (uint64_t) ga;
-      LDB_TRY(ldb_counters(ctx, 2 + GB_MAX_OUT, (uint64_t**) &d_ctl));
-      h->g_flags = (uint64_t) d_ctl;
-      // upper bound of groups = min(cap, rows) (1 for keyless); the sorted path knows the exact number
-      const uint64_t max_groups = std::max<uint64_t>(1, h->keyless ? 1 : h->dense_sorted ? sorted_groups : std::min<uint64_t>(cap, (uint64_t) in->n_rows));
-      h->dense_groups = h->dense_sorted ? max_groups : 0;
-      if (h->dense_out) {
-         LDB_TRY(attempt.alloc(&cross, (size_t) sorted_chunks + 8));
-         LDB_HIP(hipMemsetAsync(cross, 0, (size_t) sorted_chunks + 8, ctx->stream));
-         h->cross_flags = (uint64_t) cross;
-      }
-      if (h->direct || h->dense_keys) {
-         LDB_TRY(outs.alloc(&direct_keys, (size_t) h->direct_key_width * (size_t) max_groups));
-         h->direct_keys_out = (uint64_t) direct_keys;
-      }
-      if (!h->direct && h->dense_keys != 2) {
-         LDB_TRY(outs.alloc(&rep_rows, 4 * (size_t) max_groups));
-         h->rep_rows_out = (uint64_t) rep_rows;
-         // ordered slots give up on long probe runs, which depends on the insertion order: should a REPLAYED execution
-         // (ldb_readback) meet that where the recorded one did not, its group count is too high until the trace ends and the
-         // execution is repeated — the representative rows beyond the real count must then still be valid row numbers
-         if (h->ordered_slots && ctx->trace_mode == 2) LDB_HIP(hipMemsetAsync(rep_rows, 0, 4 * (size_t) max_groups, ctx->stream));
-      }
-      for (int32_t a = 0; a < n_aggs; a++) {
-         LDB_TRY(outs.alloc(&out_vals[(size_t) a], (size_t) oinfo[(size_t) a].width * (size_t) max_groups));
-         h->outs[a].out_values = (uint64_t) out_vals[(size_t) a];
-         h->outs[a].out_valid = 0;
-         if (h->outs[a].cnt_acc >= 0 || h->outs[a].cnt_rows_acc >= 0 || h->outs[a].fn == LDB_AGG_ANY) {
-            LDB_TRY(outs.alloc(&out_valid[(size_t) a], (size_t) max_groups));
-            LDB_TRY(outs.alloc(&bitmaps[(size_t) a], (size_t) ((max_groups + 7) / 8 + 1)));
-            h->outs[a].out_valid = (uint64_t) out_valid[(size_t) a];
-         }
-      }
-      LDB_TRY(d_desc.upload(h, sizeof(*h)));
-      d = d_desc.p;
-      hipLaunchKernelGGL(k_gb_init, dim3(ldb_grid_for(ctx, (int64_t) cap, 256, 8)), dim3(256), 0, ctx->stream, gk, ga, d);
-      // COUNT(*) per key over direct slots, many rows into a table far beyond the L2: partition, then count in LDS
-      const bool partitioned = h->direct && h->n_words == 1 && h->n_accs == 1 && h->n_preds == 0 && h->n_cpreds == 0 && cap >= (1ull << 20) && (cap >> GBP_SHIFT) <= GBP_MAX_PARTS &&
-         in->n_rows >= ldb_option("gb_partition_min_rows", 8ll << 20) && (uint64_t) in->n_rows < (1ull << 32) && ldb_option("gb_partition", 1) != 0;
-      // the same for arbitrary aggregates (k_gbp_agg): as many slots per partition as their accumulator words fit into 60 KB of LDS
-      uint32_t pv_shift = 0;
-      while (pv_shift < 16 && ((size_t) 8 * (size_t) nw << (pv_shift + 1)) <= 60 * 1024) pv_shift++;
-      bool wide_minmax = false;
-      for (int a = 0; a < h->n_accs; a++) wide_minmax = wide_minmax || h->accs[a].kind == ACC_MIN128 || h->accs[a].kind == ACC_MAX128;
-      const bool part_values = !partitioned && h->direct && h->n_preds == 0 && !wide_minmax && cap >= (1ull << 20) && pv_shift >= 8 && (cap >> pv_shift) <= GBP_MAX_PARTS &&
-         in->n_rows >= ldb_option("gb_partition_min_rows", 8ll << 20) && (uint64_t) in->n_rows < (1ull << 32) && ldb_option("gb_partition", 1) != 0 && ldb_option("gb_partition_values", 1) != 0;
-      if (partitioned) {
-         const uint32_t nparts = (uint32_t) (cap >> GBP_SHIFT);
-         const uint32_t g0 = (uint32_t) std::max<int64_t>(1, std::min<int64_t>((int64_t) ctx->cus, (in->n_rows + 16383) / 16384));
-         const uint64_t rows_per_wg = ((uint64_t) in->n_rows + g0 - 1) / g0;
-         const size_t hn = (size_t) nparts * g0;
-         LdbBufs tmpb(ctx);
-         uint32_t* slots;
-         if (ldb_option("gb_partition_wc", 1) != 0 && nparts > 64) {
-            // write-combining two-pass partition (ldb_wc.hip): the slots are written once as a dense array, tile-sorted by
-            // partition in LDS and stored in full-line runs — the one-pass scatter below keeps nparts open 4-byte streams per
-            // workgroup (Q13: 1 024), most of whose lines leave the L2 half written (2.4 ms for 148 M rows)
-            uint32_t *raw, *part = nullptr, chunks = 1;
-            LDB_TRY(tmpb.alloc(&raw, 4 * (size_t) in->n_rows));
-            LDB_TRY(tmpb.alloc(&slots, 4 * (size_t) in->n_rows));
-            {
-               LdbProf prof_(ctx, "k_gbp_slots");
-               hipLaunchKernelGGL(k_gbp_slots, dim3(ldb_grid_for(ctx, in->n_rows, 256, 8)), dim3(256), 0, ctx->stream, (const DGroupBy*) d, raw);
-            }
-            LDB_TRY(ldb_wc_partition(ctx, raw, nullptr, (uint64_t) in->n_rows, 0u, (uint32_t) (cap - 1), GBP_SHIFT, nparts, slots, nullptr, &part, &chunks, "k_gbp_hist", "k_gbp_scatter"));
-            tmpb.adopt(part);
-            {
-               LdbProf prof_(ctx, "k_gbp_count");
-               hipLaunchKernelGGL(k_gbp_count, dim3(nparts), dim3(GBP_BLOCK), 0, ctx->stream, (const uint32_t*) slots, (const uint32_t*) part, chunks, nparts, (uint64_t) in->n_rows,
-                                  ga + (uint64_t) h->direct_word * cap);
-            }
-         } else {
-            uint32_t *hist, *offs;
-            LDB_TRY(tmpb.alloc(&hist, 4 * hn));
-            LDB_TRY(tmpb.alloc(&offs, 4 * hn));
-            LDB_TRY(tmpb.alloc(&slots, 4 * (size_t) in->n_rows));
-            {
-               LdbProf prof_(ctx, "k_gbp_hist");
-               hipLaunchKernelGGL(k_gbp_hist, dim3(g0), dim3(GBP_SBLOCK), 0, ctx->stream, (const DGroupBy*) d, nparts, rows_per_wg, hist);
-            }
-            LDB_TRY(ldb_exclusive_scan_u32(ctx, hist, offs, (int64_t) hn, nullptr));
-            {
-               LdbProf prof_(ctx, "k_gbp_scatter");
-               hipLaunchKernelGGL(k_gbp_scatter, dim3(g0), dim3(GBP_SBLOCK), 0, ctx->stream, (const DGroupBy*) d, nparts, rows_per_wg, (const uint32_t*) offs, slots);
-            }
-            {
-               LdbProf prof_(ctx, "k_gbp_count");
-               hipLaunchKernelGGL(k_gbp_count, dim3(nparts), dim3(GBP_BLOCK), 0, ctx->stream, (const uint32_t*) slots, (const uint32_t*) offs, g0, nparts, (uint64_t) in->n_rows,
-                                  ga + (uint64_t) h->direct_word * cap);
-            }
-         }
-      } else if (part_values) {
-         // any aggregates over direct slots too many for the caches, many rows: partition (slot, row) pairs, aggregate every slot range in LDS
-         const uint32_t nparts = (uint32_t) (cap >> pv_shift);
-         uint32_t *raw, *slots, *prow, *part = nullptr, chunks = 1;
-         LdbBufs tmpb(ctx);
-         LDB_TRY(tmpb.alloc(&raw, 4 * (size_t) in->n_rows));
-         LDB_TRY(tmpb.alloc(&slots, 4 * (size_t) in->n_rows));
-         LDB_TRY(tmpb.alloc(&prow, 4 * (size_t) in->n_rows));
-         {
-            LdbProf prof_(ctx, "k_gbp_slots");
-            hipLaunchKernelGGL(k_gbp_slots, dim3(ldb_grid_for(ctx, in->n_rows, 256, 8)), dim3(256), 0, ctx->stream, (const DGroupBy*) d, raw);
-         }
-         LDB_TRY(ldb_wc_partition(ctx, raw, nullptr, (uint64_t) in->n_rows, 0u, (uint32_t) (cap - 1), pv_shift, nparts, slots, prow, &part, &chunks, "k_gbp_hist", "k_gbp_scatter"));
-         tmpb.adopt(part);
-         {
-            LdbProf prof_(ctx, "k_gbp_agg");
-            hipLaunchKernelGGL(k_gbp_agg, dim3(nparts), dim3(GBP_BLOCK), (size_t) 8 * (size_t) nw << pv_shift, ctx->stream, (const DGroupBy*) d, (const uint32_t*) slots, (const uint32_t*) prow,
-                               (const uint32_t*) part, chunks, nparts, (uint64_t) in->n_rows, pv_shift);
-         }
-      } else if (in->n_rows) {
-         int per_cu = lds_bytes > 40 * 1024 ? 2 : 4;
-         // (the sorted, LDS-free path was swept over 2 / 3 / 4 / 6 / 8 resident workgroups per CU: 5.52 / 4.22 / 3.90 / 3.70 / 3.83 ms on one box, but 6 gave 4.05 ms on the
-         // next one where 4 gives ≈ 3.95: inside the box-to-box spread, so the default stays)
-         if (const int64_t forced = ldb_option("gb_wgs_per_cu", 0)) per_cu = (int) std::max<int64_t>(1, std::min<int64_t>(forced, 16)); // experiments (Q1's line re-fetches)
-         int grid = ldb_grid_for(ctx, in->n_rows, GB_BLOCK, per_cu);
-         hipFunction_t spec = nullptr;
-         if (ldb_jit_wanted(in->n_rows)) {
-            std::string why;
-            spec = ldb_jit_groupby(ctx->device, h, &why);
-            if (!spec) ldb_set_error("groupby: specialised kernel unavailable (%s); using the generic kernel", why.c_str());
-         }
-         const char* prof_name = h->direct ? "k_groupby_direct" : "k_groupby"; // (the same kernel; the name tells the profile which slot scheme ran)
-         if (spec) {
-            LdbProf prof_(ctx, prof_name);
-            void* params[] = {(void*) &d};
-            LDB_HIP(hipModuleLaunchKernel(spec, (unsigned) grid, 1, 1, GB_BLOCK, 1, 1, (unsigned) lds_bytes, ctx->stream, params, nullptr));
-         } else {
-            LdbProf prof_(ctx, prof_name);
-            hipLaunchKernelGGL(k_groupby, dim3(grid), dim3(GB_BLOCK), lds_bytes, ctx->stream, d);
-         }
-      }
-      LDB_HIP(hipGetLastError());
-      // ---- finalize (speculative: valid only if the flags come back clean)
-      if (h->dense_out) { // every group inside one wave is final already: only the chunk-crossing groups are left, the count is known
-         LdbProf prof_(ctx, "k_gb_finalize");
-         hipLaunchKernelGGL(k_gb_finalize_cross, dim3(ldb_grid_for(ctx, (int64_t) sorted_chunks, 256, 8)), dim3(256), 0, ctx->stream, (const DGroupBy*) d, sorted_chunks,
-                            (const unsigned long long*) d_sorted_groups);
-         for (int32_t a = 0; a < n_aggs; a++)
-            if (out_valid[(size_t) a])
-               hipLaunchKernelGGL(k_pack_valid_bytes, dim3(ldb_grid_for(ctx, (int64_t) max_groups, 256 * 8, 4)), dim3(256), 0, ctx->stream, out_valid[(size_t) a], bitmaps[(size_t) a],
-                                  (const unsigned long long*) d_sorted_groups, (uint64_t) max_groups, d_ctl + 2 + a);
-         LDB_HIP(hipGetLastError());
-      } else {
-         LdbProf prof_(ctx, "k_gb_finalize");
-         const int64_t n_chunks = (int64_t) ((cap + 63) / 64);
-         LdbBufs fin(ctx);
-         uint32_t *pop = nullptr, *off;
-         LDB_TRY(fin.alloc(&off, 4 * (size_t) n_chunks));
-         const int fgrid = ldb_grid_for(ctx, (int64_t) cap, 256, 8);
-         const uint64_t* occ = h->direct ? (const uint64_t*) h->g_acc + (uint64_t) h->direct_word * cap : (const uint64_t*) h->g_keys;
-         if (ldb_option("scan_single_pass", 1) != 0) { // occupied slots per chunk + their exclusive scan + the group count: one chained launch
-            const uint64_t n_tiles = ((uint64_t) n_chunks + GBO_TILE_CHUNKS - 1) / GBO_TILE_CHUNKS;
-            ChainCall c;
-            LDB_TRY(ldb_chain_begin(ctx, n_tiles, false, &c));
-            hipLaunchKernelGGL(k_gb_occupancy_scan, dim3((unsigned) n_tiles), dim3(256), 0, ctx->stream, occ, cap, (uint64_t) n_chunks, n_tiles, off, d_ctl + 1, c.status, c.ticket, c.ticket_base,
-                               c.epoch);
-            if (hipGetLastError() != hipSuccess) return ldb_chain_failed(ctx);
-         } else {
-            LDB_TRY(fin.alloc(&pop, 4 * (size_t) n_chunks));
-            hipLaunchKernelGGL(k_gb_occupancy, dim3(fgrid), dim3(256), 0, ctx->stream, occ, cap, pop);
-            LDB_TRY(ldb_exclusive_scan_u32(ctx, pop, off, n_chunks, (uint64_t*) (d_ctl + 1)));
-         }
-         hipLaunchKernelGGL(k_gb_finalize, dim3(fgrid), dim3(256), 0, ctx->stream, d, rep_rows, (const uint32_t*) off);
-         for (int32_t a = 0; a < n_aggs; a++)
-            if (out_valid[(size_t) a])
-               hipLaunchKernelGGL(k_pack_valid_bytes, dim3(ldb_grid_for(ctx, (int64_t) max_groups, 256 * 8, 4)), dim3(256), 0, ctx->stream, out_valid[(size_t) a], bitmaps[(size_t) a],
-                                  (const unsigned long long*) (d_ctl + 1), (uint64_t) max_groups, d_ctl + 2 + a);
-         LDB_HIP(hipGetLastError());
-      }
-      static_assert(sizeof(ctl) <= 64 * sizeof(int64_t), "control block must fit the pinned scratch words");
-      LDB_TRY(LDB_READBACK(ctx, ctl, d_ctl, ctl_bytes));
-      if (h->dense_out) ctl[1] = sorted_groups; // (no occupancy scan ran: the heads pass counted the groups)
-      d_desc.release();
-      const uint64_t flags = (uint64_t) ctl[0];
-      if ((flags & 3) == 0) break;
-      outs.free_all();
-      rep_rows = nullptr;
-      direct_keys = nullptr;
-      out_vals.assign((size_t) n_aggs, nullptr);
-      out_valid.assign((size_t) n_aggs, nullptr);
-      bitmaps.assign((size_t) n_aggs, nullptr);
-      if ((flags & 2) && h->ordered_slots) { // long probe runs: this key distribution needs hashed slots
-         h->ordered_slots = 0;
-         in->sides[(size_t) keys[0].side].table->cols[(size_t) keys[0].col].skewed = true;
-         if ((flags & 1) == 0) continue;
-      }
-      // global table overflowed: retry larger (the estimate was too low)
-      if (cap >= cap_max) LDB_FAIL(LDB_ERR_HIP, "groupby: global table overflow at maximum capacity");
-      cap = std::min(cap * 8, cap_max);
-   }
-   sorted_tmp.free(chunk_off);
-   n_groups = (uint64_t) ctl[1];
-   for (int32_t a = 0; a < n_aggs; a++) outs.free(out_valid[(size_t) a]);
-
-   // ---- result table: key columns = gather of representative rows, then aggregates
-   res->n_rows = (int64_t) n_groups;
-   res->cols.resize((size_t) (n_keys + n_aggs));
-   if (h->direct || h->dense_keys) { // the key column was written by k_gb_finalize / by the sorted aggregation itself
-      ldb_column& kc = res->cols[0];
-      kc.name = direct_src->name;
-      kc.type = direct_src->type;
-      kc.width = direct_src->width;
-      kc.values = direct_keys;
-      outs.keep(direct_keys);
-      kc.value_bytes = (int64_t) n_groups * kc.width;
-      kc.owned = true;
-      if (direct_src->has_range) { // the groups' keys are values of the source column: its cached range stays a valid superset
-         kc.has_range = true;
-         kc.vmin = direct_src->vmin;
-         kc.vmax = direct_src->vmax;
-      }
-      outs.free(rep_rows); // (sorted keys with an ANY aggregate: the representative rows were only read by the finalisation)
-   } else {
-      LdbRelHold reps(ctx);
-      outs.keep(rep_rows); // (ldb_rel_select takes the selection over)
-      LDB_TRY(ldb_rel_select(ctx, in, rep_rows, (int64_t) n_groups, &reps.r));
-      if (n_keys) LDB_TRY(ldb_gather_columns(ctx, reps.r, keys, n_keys, res->cols.data()));
-   }
-   for (int32_t a = 0; a < n_aggs; a++) {
-      ldb_column& c = res->cols[(size_t) (n_keys + a)];
-      char nm[32];
-      snprintf(nm, sizeof(nm), "agg%d", a);
-      c.name = nm;
-      c.type = oinfo[(size_t) a].type;
-      c.width = oinfo[(size_t) a].width;
-      c.values = out_vals[(size_t) a];
-      outs.keep(c.values);
-      c.value_bytes = (int64_t) n_groups * c.width;
-      c.owned = true;
-      if (is_str[(size_t) a]) { // a LAZY utf8 column (ldb_column_is_lazy): the codes the kernels wrote + the argument column's dictionary
-         const ldb_column& sc = in->sides[(size_t) str_ref[(size_t) a].side].table->cols[(size_t) str_ref[(size_t) a].col];
-         c.type = sc.type;
-         c.type.nullable = 1;
-         c.width = sc.width;
-         c.dict_codes = (uint32_t*) c.values;
-         c.values = nullptr;
-         c.value_bytes = -1;
-         c.dict = sc.dict;
-         c.dict->dict_refs++;
-         c.dict_size = sc.dict_size;
-         c.dict_pred_cache = new std::unordered_map<std::string, std::string>();
-      }
-      if (bitmaps[(size_t) a]) { // drop the bitmap when nothing is NULL
-         const int64_t nulls = (int64_t) ctl[2 + a];
-         if (nulls) {
-            c.validity = bitmaps[(size_t) a];
-            outs.keep(c.validity);
-            c.null_count = nulls;
-         } else {
-            outs.free(bitmaps[(size_t) a]);
-         }
-      }
-   }
-   LDB_HIP(hipGetLastError());
-   *out = res.release();
-   return LDB_OK;
+   GbState s{ctx, in, keys, n_keys, aggs, n_aggs, is_str, str_ref, h, {in, h, {}}, LdbBufs(ctx), LdbBufs(ctx)};
+   s.forget_outputs();
+   LDB_TRY(s.lower_aggs());
+   s.g = gb_geometry(h, est_groups, in->n_rows);
+   LDB_TRY(s.choose_layout());
+   GbVerdict v = GB_RETRY_LARGER; // (nothing attempted yet)
+   while (v != GB_DONE) LDB_TRY(s.attempt(&v));
+   s.sorted_tmp.free(s.chunk_off);
+   for (int32_t a = 0; a < n_aggs; a++) s.outs.free(s.out_valid[(size_t) a]);
+   return s.result_table(out);
 }

@@ -436,6 +436,20 @@ int32_t ldb_dict_rewrite_pred(const ldb_rel* r, const ldb_filter_desc* p, DPred*
 #define LDB_DICT_MAX 1024 /* codes per dictionary = bits of DPred::in_blob */
 int32_t ldb_width_of(const ldb_coltype& t, int narrow);
 
+static inline uint64_t next_pow2_u64(uint64_t v) {
+   uint64_t p = 1;
+   while (p < v) p <<= 1;
+   return p;
+}
+// out[i] = i (ldb_core.hip); launched from several translation units — host launches only, never called from device code (no -fgpu-rdc)
+__global__ void k_iota_u32(uint32_t* out, uint64_t n);
+// the rows of `in` that sel[0, n_sel) names, as a relation of its own — takes `sel` over, on error returns too (ldb_scan.hip); their columns
+// `refs` materialised into outs[0, n_cols) (ldb_core.hip)
+int32_t ldb_rel_select(ldb_ctx* ctx, ldb_rel* in, uint32_t* sel, int64_t n_sel, ldb_rel** out);
+int32_t ldb_gather_columns(ldb_ctx* ctx, const ldb_rel* r, const ldb_colref* refs, int32_t n_cols, ldb_column* outs);
+// MIN / MAX over utf8 columns — a selection row per aggregate: the extreme string's row, LDB_NULL_ROW when every argument is NULL (ldb_strminmax.hip)
+int32_t ldb_str_minmax(ldb_ctx* ctx, const ldb_rel* in, const ldb_colref* cols, const int32_t* is_max, int32_t n, uint32_t** sel_out);
+
 // launch geometry: blocks for a grid-stride kernel over n items
 static inline int ldb_grid_for(const ldb_ctx* ctx, int64_t n, int block, int per_cu) {
    int64_t want = (n + block - 1) / block;

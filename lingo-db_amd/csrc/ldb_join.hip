@@ -257,42 +257,6 @@ bool ldb_join_jit_check(std::string* log) {
 }
 
 // ---------------------------------------------------------------- small helper kernels
-__global__ void k_word_pop(const uint64_t* __restrict__ bitmap, uint32_t* __restrict__ pop, uint64_t n_words) {
-   for (uint64_t w = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x; w < n_words; w += (uint64_t) gridDim.x * blockDim.x) pop[w] = (uint32_t) __popcll(bitmap[w]);
-}
-// bitmap → ascending row ids: one wave per 64-bit word, offsets from a device scan of the word popcounts
-__global__ void k_bitmap_expand(const uint64_t* __restrict__ bitmap, const uint32_t* __restrict__ word_off, uint32_t* __restrict__ out, uint64_t n_words) {
-   const uint32_t lane = threadIdx.x & 63;
-   const uint64_t wave = (blockIdx.x * (uint64_t) blockDim.x + threadIdx.x) >> 6;
-   const uint64_t n_waves = ((uint64_t) gridDim.x * blockDim.x) >> 6;
-   for (uint64_t w = wave; w < n_words; w += n_waves) {
-      uint64_t m = bitmap[w];
-      if ((m >> lane) & 1) out[word_off[w] + d_rank_in(m)] = (uint32_t) (w * 64 + lane);
-   }
-}
-// the same for SPARSE bitmaps: one LANE per word — a wave reads 64 words with one coalesced load and only the lanes whose
-// word is non-zero write (a wave per word spends a whole iteration on every empty word: 9.4 M iterations for a 600 M-row
-// probe of which 95 % produce nothing)
-__global__ void k_bitmap_expand_sparse(const uint64_t* __restrict__ bitmap, const uint32_t* __restrict__ word_off, uint32_t* __restrict__ out, uint64_t n_words) {
-   for (uint64_t w = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x; w < n_words; w += (uint64_t) gridDim.x * blockDim.x) {
-      uint64_t m = bitmap[w];
-      if (!m) continue;
-      uint32_t at = word_off[w];
-      const uint32_t base = (uint32_t) (w * 64);
-      while (m) {
-         out[at++] = base + (uint32_t) __builtin_ctzll(m);
-         m &= m - 1;
-      }
-   }
-}
-// picks the scheme by density: fewer than one set bit in eight → lane per word
-static void launch_bitmap_expand(ldb_ctx* ctx, const uint64_t* bitmap, const uint32_t* off, uint32_t* out, int64_t n_words, uint64_t total) {
-   if (total * 8 < (uint64_t) n_words * 64) hipLaunchKernelGGL(k_bitmap_expand_sparse, dim3(ldb_grid_for(ctx, n_words, 256, 8)), dim3(256), 0, ctx->stream, bitmap, off, out, (uint64_t) n_words);
-   else hipLaunchKernelGGL(k_bitmap_expand, dim3(ldb_grid_for(ctx, n_words * 64, 256, 8)), dim3(256), 0, ctx->stream, bitmap, off, out, (uint64_t) n_words);
-}
-__global__ void k_iota_u32j(uint32_t* out, uint64_t n) {
-   for (uint64_t i = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x; i < n; i += (uint64_t) gridDim.x * blockDim.x) out[i] = (uint32_t) i;
-}
 // out[j] = ids[sel[j]] with LDB_NULL_ROW passthrough
 // all-match shortcut of a replayed unique probe: match[] of a row whose bitmap bit is clear was never written
 __global__ void k_unmatched_to_zero(const uint64_t* __restrict__ bitmap, uint32_t* __restrict__ match, uint64_t n) {
@@ -634,15 +598,295 @@ static void radix_strip(ldb_ctx* ctx, ldb_rel* r) {
    r->sides.erase(r->sides.begin());
 }
 
-static uint64_t next_pow2_u64(uint64_t v) {
-   uint64_t p = 1;
-   while (p < v) p <<= 1;
-   return p;
+// ---------------------------------------------------------------- build
+// The one copy of a table's layout into a kernel descriptor: every insert pass and make_probe_desc go through it.  What differs between
+// build and probe stays with the callers: pair32 (1 or 2 on the probe side), rank_sorted, build_unique, the coarse filter's admission test.
+static void ldb_ht_layout(const ldb_hashtable* ht, DJoin* h) {
+   h->cap = ht->cap;
+   h->slots = (uint64_t) ht->slots;
+   h->key32 = ht->key32;
+   h->ordered_slots = ht->ordered_slots;
+   h->direct = ht->direct;
+   h->kmin = ht->kmin;
+   h->kmax = ht->kmax;
+   h->kmult = ht->kmult;
+   h->kmult32 = ht->kmult32;
+   h->ksh = ht->ksh;
+   h->slot32 = ht->ordered_slots ? ht->slot32 : 0;
+   h->key_bits = (uint64_t) ht->key_bits;
+   h->has_key_bits = ht->key_bits ? 1 : 0;
+   h->chained = ht->chained;
+   h->next = (uint64_t) ht->next;
 }
 
-int32_t ldb_rel_select(ldb_ctx* ctx, ldb_rel* in, uint32_t* sel, int64_t n_sel, ldb_rel** out);
+// The LDS-resident coarse filter of a rank table (DJoin::has_coarse): one bit per 2^shift key values, `cwords` 32-bit words; want = build it.
+// At most 40 KB (four 512-thread workgroups per CU) and worth it when most 64-key blocks are empty.
+// Round 6: one bit per SIXTEEN key values where that pays.  p(g) = 1 - (1 - density)^g is the share of probes a g-key filter lets
+// through to the L2.  Q9's green parts (5.4 % of the key range): p(64) = 0.97 — useless — p(16) = 0.59; Q8's part filter (0.67 %):
+// 0.35 against 0.10.  The fine filter of a 20 M key range is 156 KB: ONE 1024-thread workgroup per CU instead of four of 512 — taken
+// when the coarse one would pass more than a quarter of the probes; where the fine filter itself fits 40 KB it simply replaces the
+// coarse one.  Option join_coarse_fine (default 1).
+struct JoinCoarsePlan {
+   bool want;
+   uint32_t shift;
+   uint64_t cwords;
+};
+static JoinCoarsePlan join_coarse_plan(unsigned __int128 range0, uint64_t distinct) {
+   uint32_t shift = 6;
+   uint64_t cwords = (uint64_t) (range0 / 64 / 32) + 1;
+   const double density = range0 > 0 ? (double) distinct / (double) range0 : 1.0;
+   const double pass64 = 1.0 - pow(1.0 - density, 64.0), pass16 = 1.0 - pow(1.0 - density, 16.0);
+   const bool coarse_on = ldb_option("join_coarse", 1) != 0;
+   bool want = coarse_on && cwords * 4 <= 40 * 1024 && (unsigned __int128) distinct * 64 * 2 <= range0;
+   if (coarse_on && ldb_option("join_coarse_fine", 1) != 0 && pass16 <= 0.7) {
+      const uint64_t fine_words = (uint64_t) (range0 / 16 / 32) + 1;
+      const bool small = fine_words * 4 <= 40 * 1024;
+      if (small || (fine_words * 4 <= 156 * 1024 && (!want || pass64 > 0.25))) {
+         shift = 4;
+         cwords = fine_words;
+         want = true;
+      }
+   }
+   // … and where a still finer one fits beside the tile kernels' queue (<= 16 KB: a supplier-sized key range), the finest that does: Q21's 4 %
+   // of the 1 M supplier keys pass 48 % of the probes at 16 keys per bit, 28 % at 8; Q7's 8 %: 74 → 49 %.  (0 = the presence bits themselves.)
+   if (coarse_on && ldb_option("join_coarse_finest", 1) != 0 && want && shift == 4 && cwords * 4 <= 16 * 1024) {
+      while (shift > 0 && ((uint64_t) (range0 >> (shift - 1)) / 32 + 1) * 4 <= 16 * 1024 && 1.0 - pow(1.0 - density, (double) (1u << shift)) > 0.1) shift--;
+      cwords = (uint64_t) (range0 >> shift) / 32 + 1;
+   }
+   return {want, shift, cwords};
+}
 
-// ---------------------------------------------------------------- build
+// both key columns of a two-key join are 4-byte integers: the pair fits one slot word (DJoin::pair32)
+static bool join_pair_narrow(const DKeys& keys) {
+   bool narrow = true;
+   for (int k = 0; k < 2; k++) narrow = narrow && keys.cols[k].width == 4 && (keys.cols[k].type == LDB_T_INT32 || keys.cols[k].type == LDB_T_DATE32 || keys.cols[k].type == LDB_T_CHAR4);
+   return narrow;
+}
+// what the phases of one ldb_gpu_join_build call share, and the phases
+struct JoinBuild {
+   ldb_ctx* ctx;
+   ldb_rel* build;
+   ldb_hashtable* ht;
+   DJoin* h;
+   int32_t n_keys;
+   int32_t build_unique; // the caller's promise, until a pass sees a duplicate
+   uint32_t* dflags = nullptr; // the flag word the passes write: a zeroed arena word, a fresh one for every pass instead of a clear
+   long long lo = 0, hi = -1; // range of the (single, integer) build key; empty = not known / no non-NULL key
+   unsigned __int128 range0 = 0; // its number of values
+   int64_t n_rows() const { return build->n_rows; }
+   bool fits_int32() const { return lo >= INT32_MIN && hi <= INT32_MAX; }
+   int32_t fresh_flags() {
+      LDB_TRY(ldb_counters(ctx, 1, (uint64_t**) &dflags));
+      h->flags = (uint64_t) dflags;
+      return LDB_OK;
+   }
+   // one bit per key value of the build key range (DJoin::has_key_bits)
+   int32_t alloc_key_bits() {
+      const size_t words = (size_t) ((range0 + 31) / 32);
+      LDB_TRY(LdbBufs::alloc_into(ctx, &ht->key_bits, 4 * words));
+      LDB_HIP(hipMemsetAsync(ht->key_bits, 0, 4 * words, ctx->stream));
+      return LDB_OK;
+   }
+
+   // the key column's cached statistic (a superset of the build rows' range, free after its first use) when it has one; otherwise one pass
+   // over the build keys
+   int32_t key_range(const ldb_colref* keys) {
+      long long got[2];
+      const ldb_table* kt = build->sides[(size_t) keys[0].side].table;
+      int64_t clo = 0, chi = -1;
+      if (!kt->cols[(size_t) keys[0].col].validity && ldb_column_range(ctx, kt, keys[0].col, &clo, &chi) == LDB_OK && clo <= chi) {
+         got[0] = clo;
+         got[1] = chi;
+      } else {
+         long long* range = (long long*) (ctx->d_scratch + 32);
+         const long long init[2] = {INT64_MAX, INT64_MIN};
+         LDB_TRY(ldb_h2d_small(ctx, range, init, 16));
+         LdbDesc<DJoin> dr_desc(ctx);
+         LDB_TRY(dr_desc.upload(h, sizeof(*h)));
+         hipLaunchKernelGGL(k_join_key_range, dim3(ldb_grid_for(ctx, n_rows(), 256, 8)), dim3(256), 0, ctx->stream, dr_desc.p, range);
+         LDB_TRY(LDB_READBACK(ctx, got, range, 16));
+      }
+      lo = got[0];
+      hi = got[1];
+      range0 = got[0] <= got[1] ? (unsigned __int128) ((__int128) got[1] - got[0]) + 1 : 0;
+      return LDB_OK;
+   }
+
+   // RANK-BITMAP table for (promised) unique keys over a range of at most 64 values per build row — or any build side over
+   // a range of at most 2^26 values (a 16 MB table: a selective filter on a dimension table, Q17's 20 k of 20 M parts):
+   // range / 4 bytes, one 8-byte load per probe, no collisions, nothing to clear but the words (DJoin::direct == 2)
+   // *built: the table is finished.  Else the keys repeat — the promise does not hold (it is withdrawn in b) and the general layouts follow.
+   int32_t build_rank(bool* built) {
+      *built = false;
+      const bool eligible = range0 > 0 && build_unique && ldb_option("join_direct", 1) != 0 && ldb_option("join_rank", 1) != 0 && range0 <= ((unsigned __int128) 1 << 32) &&
+         (range0 <= (unsigned __int128) std::max<int64_t>(4096, 64 * n_rows()) || range0 <= ((unsigned __int128) 1 << 26)) && fits_int32() && n_rows() < (int64_t) LDB_NULL_ROW;
+      if (!eligible) return LDB_OK;
+      const uint64_t n_words = (uint64_t) (range0 / 32) + 1;
+      LDB_TRY(LdbBufs::alloc_into(ctx, &ht->slots, 8 * (size_t) n_words)); // (owned by the table object: freed on every error return)
+      uint64_t* tab = ht->slots;
+      LDB_HIP(hipMemsetAsync(tab, 0, 8 * (size_t) n_words, ctx->stream));
+      unsigned long long* counter;
+      LDB_TRY(ldb_counters(ctx, 3, (uint64_t**) &counter));
+      uint64_t* d_total = (uint64_t*) (counter + 2);
+      h->direct = 2;
+      h->kmin = lo;
+      h->kmax = hi;
+      h->slots = (uint64_t) tab;
+      h->counter = (uint64_t) counter;
+      LdbDesc<DJoin> dr_desc(ctx);
+      LDB_TRY(dr_desc.upload(h, sizeof(*h)));
+      DJoin* dr = dr_desc.p;
+      {
+         LdbProf prof_(ctx, "k_join_build");
+         hipLaunchKernelGGL(k_join_rank_bits, dim3(ldb_grid_for(ctx, n_rows(), 256, 8)), dim3(256), 0, ctx->stream, dr);
+         // popcounts → scan → prefix halves, one launch
+         const uint64_t n_tiles = (n_words + CHAIN_TILE - 1) / CHAIN_TILE;
+         ChainCall c;
+         LDB_TRY(ldb_chain_begin(ctx, n_tiles, false, &c));
+         hipLaunchKernelGGL(k_rank_prefix_chain, dim3((unsigned) n_tiles), dim3(256), 0, ctx->stream, tab, n_words, n_tiles, (unsigned long long*) d_total, c.status, c.ticket, c.ticket_base, c.epoch);
+         if (hipGetLastError() != hipSuccess) return ldb_chain_failed(ctx);
+      }
+      uint64_t back[3] = {0, 0, 0}; // non-NULL keys, —, distinct keys
+      uint32_t fl[2] = {0, 0};
+      LDB_TRY(LDB_READBACK(ctx, back, counter, 24));
+      LDB_TRY(LDB_READBACK(ctx, fl, dflags, 8));
+      if (back[0] == back[2]) { // every non-NULL key set a bit of its own: unique
+         *built = true;
+         ht->direct = 2;
+         ht->kmin = lo;
+         ht->kmax = hi;
+         ht->cap = (uint64_t) range0;
+         ht->slot_bytes = 8 * (size_t) n_words;
+         ht->rank_sorted = (fl[0] & 4u) ? 0 : 1;
+         const JoinCoarsePlan cp = join_coarse_plan(range0, back[2]);
+         if (cp.want) {
+            LDB_TRY(LdbBufs::alloc_into(ctx, &ht->coarse, 4 * (size_t) cp.cwords));
+            ht->coarse_words = (uint32_t) cp.cwords;
+            ht->coarse_shift = cp.shift;
+            hipLaunchKernelGGL(k_rank_coarse, dim3((unsigned) ((cp.cwords + 255) / 256)), dim3(256), 0, ctx->stream, (const uint64_t*) tab, n_words, ht->coarse, (uint32_t) cp.cwords, cp.shift);
+            LDB_HIP(hipGetLastError());
+         }
+         if (!ht->rank_sorted) { // a key's rank is not its build row: next[] = rank → row
+            LDB_TRY(LdbBufs::alloc_into(ctx, &ht->next, 4 * (size_t) (n_rows() ? n_rows() : 1)));
+            h->next = (uint64_t) ht->next;
+            LdbDesc<DJoin> dp_desc(ctx);
+            LDB_TRY(dp_desc.upload(h, sizeof(*h)));
+            hipLaunchKernelGGL(k_join_rank_perm, dim3(ldb_grid_for(ctx, n_rows(), 256, 8)), dim3(256), 0, ctx->stream, dp_desc.p);
+            LDB_HIP(hipGetLastError());
+         }
+      } else { // duplicate keys
+         LdbBufs::drop(ctx, &ht->slots);
+         h->direct = 0;
+         h->slots = 0;
+         h->counter = 0;
+         ht->unique = 0;
+         build_unique = 0;
+      }
+      dr_desc.release();
+      return fresh_flags(); // (the passes that follow start from clean flags)
+   }
+
+   // direct, ordered or hashed slots (+ key bits), then whether the rows chain from the start and whether two narrow keys live in the slot
+   int32_t choose_slots() {
+      // DIRECT addressing when the key range is at most a few times the build rows (primary keys, and filtered subsets of one): the table is
+      // then no larger than the open-addressing array it replaces (4 B x range against 8 B x nextPow2(2n) in [16n, 32n) bytes) and a probe
+      // is one 4-byte load
+      if (range0 > 0 && ldb_option("join_direct", 1) != 0 && range0 <= (unsigned __int128) std::max<int64_t>(1024, 8 * n_rows()) && range0 < ((unsigned __int128) 1 << 31) &&
+          fits_int32()) {
+         ht->direct = 1;
+         ht->kmin = lo;
+         ht->kmax = hi;
+         ht->cap = (uint64_t) range0;
+         // key bits: 32x smaller than the table, L2-resident for selective builds
+         if (range0 <= ((unsigned __int128) 1 << 27) && range0 >= 4096) LDB_TRY(alloc_key_bits());
+      } else if (lo <= hi) { // at least one non-NULL key: slots in key order (DJoin::ordered_slots)
+         ht->ordered_slots = 1;
+         ht->kmin = lo;
+         ht->kmax = hi;
+         ht->kmult = (uint64_t) ((((unsigned __int128) ht->cap) << 32) / range0);
+         // 32-bit slot arithmetic: slot = mulhi32((key - kmin) << ksh, kmult32) with (range << ksh) in [cap, 2 cap)
+         if (ht->cap <= (1ull << 31) && range0 <= ((unsigned __int128) 1 << 32) && fits_int32()) {
+            const uint64_t range = (uint64_t) range0;
+            uint32_t ksh = 0;
+            while ((range << ksh) < ht->cap) ksh++;
+            const unsigned __int128 km = (((unsigned __int128) ht->cap) << 32) / (unsigned __int128) (range << ksh);
+            ht->kmult32 = km > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t) km;
+            ht->ksh = ksh;
+            ht->slot32 = 1;
+         }
+         if (range0 <= ((unsigned __int128) 1 << 27)) LDB_TRY(alloc_key_bits()); // <= 16 MB of bits: fits the L2 comfortably
+      }
+      const bool force_chained = ldb_option("join_chained", 0) == 1; // tests
+      if (force_chained && !ht->direct) {
+         ht->ordered_slots = 0;
+         LdbBufs::drop(ctx, &ht->key_bits);
+      }
+      if (force_chained || (ht->direct && !build_unique)) { // a direct table without the promise of unique keys chains from the start
+         ht->chained = 1;
+         LDB_TRY(LdbBufs::alloc_into(ctx, &ht->next, 4 * (size_t) (n_rows() ? n_rows() : 1)));
+      }
+      // two 4-byte integer keys, open addressing: the key values live in the slot (DJoin::pair32)
+      if (!ht->direct && !ht->chained && n_keys == 2 && ldb_option("join_pair32", 1) != 0) {
+         ht->pair32 = join_pair_narrow(h->bkeys) ? 1 : 0;
+      }
+      return LDB_OK;
+   }
+
+   // the next insert pass starts from empty slots and clean flags
+   int32_t insert_reset() {
+      LDB_HIP(hipMemsetAsync(ht->slots, 0, ht->slot_bytes, ctx->stream));
+      return fresh_flags();
+   }
+   // up to three passes: ordered slots → hashed slots (skewed key range) → chained (a key repeats so often that one slot per row gives long
+   // runs); each pass stops early when it sees such a run
+   int32_t insert() {
+      ht->slot_bytes = (ht->direct ? 4 : ht->pair32 ? 16 : 8) * (size_t) ht->cap;
+      LDB_TRY(LdbBufs::alloc_into(ctx, &ht->slots, ht->slot_bytes));
+      LDB_HIP(hipMemsetAsync(ht->slots, 0, ht->slot_bytes, ctx->stream));
+      for (int attempt = 0; attempt < 3; attempt++) {
+         if (ht->chained) ht->pair32 = 0; // (a chained rebuild uses the first cap words of the same allocation)
+         ldb_ht_layout(ht, h);
+         h->pair32 = ht->pair32; // (0 / 1 here; the probe side refines 1 into 1 or 2)
+         LdbDesc<DJoin> d_desc(ctx);
+         LDB_TRY(d_desc.upload(h, sizeof(*h)));
+         DJoin* d = d_desc.p;
+         if (n_rows() && h->has_key_bits && (h->ordered_slots || h->direct)) hipLaunchKernelGGL(k_join_key_bits, dim3(ldb_grid_for(ctx, n_rows(), 256, 8)), dim3(256), 0, ctx->stream, d);
+         if (n_rows()) LDB_TRY(launch_join(ctx, h, d, ldb_grid_for(ctx, n_rows(), 256, 8), "k_join_build", "k_join_build_spec", k_join_build));
+         d_desc.release();
+         uint64_t f = 0;
+         // open addressing: which insertion meets a long run depends on the order the insertions happen in, but whether ANY does is in practice
+         // a property of the keys (a run of 512 needs hundreds of equal or colliding keys: then some insertion walks it in every order).  The
+         // flag is replayed like any count — round 4 read it for real in every execution, one stream wait in the middle of every plan with an
+         // open-addressing build (Q18: 11.5 of 13.8 ms of host time blocked in this call) — and a run that does come out differently is caught
+         // by the comparison at the trace's end like any other mis-speculation: the execution is void (an insertion that gave up dropped its row)
+         // and is repeated.  Such repeats are counted apart (LDB_RB_ORDER_DEPENDENT → ldb_gpu_order_dependent_misses, bench.py's prepared_plans
+         // block): a key distribution that sits on the run-length threshold shows there instead of hiding among data-dependent misses
+         LDB_TRY(ldb_read_u64_at(ctx, dflags, &f, LDB_SITE, LDB_RB_ORDER_DEPENDENT));
+         if (ht->direct && (f & 1) && !ht->chained) { // duplicate keys in a direct table: chain them
+            ht->chained = 1;
+            LDB_TRY(LdbBufs::alloc_into(ctx, &ht->next, 4 * (size_t) n_rows()));
+            LDB_TRY(insert_reset());
+            continue;
+         }
+         if ((f & 2) && !ht->chained) {
+            if (ht->ordered_slots) { // this key distribution needs hashed slots
+               ht->ordered_slots = 0;
+               LdbBufs::drop(ctx, &ht->key_bits);
+            } else { // hashed and still long runs: duplicates → chain them
+               ht->chained = 1;
+               LDB_TRY(LdbBufs::alloc_into(ctx, &ht->next, 4 * (size_t) n_rows()));
+            }
+            LDB_TRY(insert_reset());
+            continue;
+         }
+         // the caller's promise of unique keys is verified: duplicates fall back to the general probe
+         if ((f & 1) || ht->chained) ht->unique = 0;
+         break;
+      }
+      return LDB_OK;
+   }
+};
+
 extern "C" int32_t ldb_gpu_join_build(ldb_ctx* ctx, ldb_rel* build, const ldb_colref* keys, int32_t n_keys, int32_t build_unique, ldb_hashtable** out) {
    if (!ctx || !build || !out || n_keys < 1) LDB_FAIL(LDB_ERR_INVALID, "join_build: bad argument");
    LDB_TRY(ldb_rel_force(ctx, build)); // the table is sized from the exact row count
@@ -660,259 +904,21 @@ extern "C" int32_t ldb_gpu_join_build(ldb_ctx* ctx, ldb_rel* build, const ldb_co
    ht->cap = std::max<uint64_t>(64, next_pow2_u64((uint64_t) build->n_rows * 2));
    h->n_rows = (uint64_t) build->n_rows;
    h->key32 = ht->key32;
-   // flags / counters: zeroed words of the context's arena (ldb_counters) — fresh ones for every pass instead of a clear
-   uint32_t* dflags;
-   LDB_TRY(ldb_counters(ctx, 1, (uint64_t**) &dflags));
-   h->flags = (uint64_t) dflags;
    h->has_flags = 1;
-   // KEY32: slots in key order (see DJoin::ordered_slots) — needs the build key range first
-   const bool ordered_enabled = ldb_option("join_ordered", 1) != 0;
-   if (ht->key32 && ordered_enabled && build->n_rows > 0) {
-      long long got[2];
-      // the key column's cached statistic (a superset of the build rows' range, free after its first
-      // use) when it has one; otherwise one pass over the build keys
-      const ldb_table* kt = build->sides[(size_t) keys[0].side].table;
-      int64_t clo = 0, chi = -1;
-      if (!kt->cols[(size_t) keys[0].col].validity && ldb_column_range(ctx, kt, keys[0].col, &clo, &chi) == LDB_OK && clo <= chi) {
-         got[0] = clo;
-         got[1] = chi;
-      } else {
-         long long* range = (long long*) (ctx->d_scratch + 32);
-         const long long init[2] = {INT64_MAX, INT64_MIN};
-         LDB_TRY(ldb_h2d_small(ctx, range, init, 16));
-         LdbDesc<DJoin> dr_desc(ctx);
-         LDB_TRY(dr_desc.upload(h, sizeof(*h)));
-         DJoin* dr = dr_desc.p;
-         hipLaunchKernelGGL(k_join_key_range, dim3(ldb_grid_for(ctx, build->n_rows, 256, 8)), dim3(256), 0, ctx->stream, dr, range);
-         LDB_TRY(LDB_READBACK(ctx, got, range, 16));
-         dr_desc.release();
-      }
-      // DIRECT addressing when the key range is at most a few times the build rows (primary keys, and
-      // filtered subsets of one): the table is then no larger than the open-addressing array it replaces
-      // (4 B x range against 8 B x nextPow2(2n) in [16n, 32n) bytes) and a probe is one 4-byte load
-      const unsigned __int128 range0 = got[0] <= got[1] ? (unsigned __int128) ((__int128) got[1] - got[0]) + 1 : 0;
-      // RANK-BITMAP table for (promised) unique keys over a range of at most 64 values per build row — or any build side over
-      // a range of at most 2^26 values (a 16 MB table: a selective filter on a dimension table, Q17's 20 k of 20 M parts):
-      // range / 4 bytes, one 8-byte load per probe, no collisions, nothing to clear but the words (DJoin::direct == 2)
-      bool ranked = false;
-      if (range0 > 0 && build_unique && ldb_option("join_direct", 1) != 0 && ldb_option("join_rank", 1) != 0 && range0 <= ((unsigned __int128) 1 << 32) &&
-          (range0 <= (unsigned __int128) std::max<int64_t>(4096, 64 * build->n_rows) || range0 <= ((unsigned __int128) 1 << 26)) && got[0] >= INT32_MIN && got[1] <= INT32_MAX && build->n_rows < (int64_t) LDB_NULL_ROW) {
-         const uint64_t n_words = (uint64_t) (range0 / 32) + 1;
-         LDB_TRY(LdbBufs::alloc_into(ctx, &ht->slots, 8 * (size_t) n_words)); // (owned by the table object: freed on every error return)
-         uint64_t* tab = ht->slots;
-         LDB_HIP(hipMemsetAsync(tab, 0, 8 * (size_t) n_words, ctx->stream));
-         unsigned long long* counter;
-         LDB_TRY(ldb_counters(ctx, 3, (uint64_t**) &counter));
-         uint64_t* d_total = (uint64_t*) (counter + 2);
-         h->direct = 2;
-         h->kmin = got[0];
-         h->kmax = got[1];
-         h->slots = (uint64_t) tab;
-         h->counter = (uint64_t) counter;
-         LdbDesc<DJoin> dr_desc(ctx);
-         LDB_TRY(dr_desc.upload(h, sizeof(*h)));
-         DJoin* dr = dr_desc.p;
-         {
-            LdbProf prof_(ctx, "k_join_build");
-            hipLaunchKernelGGL(k_join_rank_bits, dim3(ldb_grid_for(ctx, build->n_rows, 256, 8)), dim3(256), 0, ctx->stream, dr);
-            // popcounts → scan → prefix halves, one launch
-            const uint64_t n_tiles = (n_words + CHAIN_TILE - 1) / CHAIN_TILE;
-            ChainCall c;
-            LDB_TRY(ldb_chain_begin(ctx, n_tiles, false, &c));
-            hipLaunchKernelGGL(k_rank_prefix_chain, dim3((unsigned) n_tiles), dim3(256), 0, ctx->stream, tab, n_words, n_tiles, (unsigned long long*) d_total, c.status, c.ticket, c.ticket_base, c.epoch);
-            if (hipGetLastError() != hipSuccess) return ldb_chain_failed(ctx);
-         }
-         uint64_t back[3] = {0, 0, 0}; // non-NULL keys, —, distinct keys
-         uint32_t fl[2] = {0, 0};
-         LDB_TRY(LDB_READBACK(ctx, back, counter, 24));
-         LDB_TRY(LDB_READBACK(ctx, fl, dflags, 8));
-         if (back[0] == back[2]) { // every non-NULL key set a bit of its own: unique
-            ranked = true;
-            ht->direct = 2;
-            ht->kmin = got[0];
-            ht->kmax = got[1];
-            ht->cap = (uint64_t) range0;
-            ht->slot_bytes = 8 * (size_t) n_words;
-            ht->rank_sorted = (fl[0] & 4u) ? 0 : 1;
-            // the LDS-resident coarse filter for selective builds over a small key range (DJoin::has_coarse): at most 40 KB
-            // (four 512-thread workgroups per CU) and worth it when most 64-key blocks are empty
-            // Round 6: one bit per SIXTEEN key values where that pays.  p(g) = 1 - (1 - density)^g is the share of probes a g-key filter lets
-            // through to the L2.  Q9's green parts (5.4 % of the key range): p(64) = 0.97 — useless — p(16) = 0.59; Q8's part filter (0.67 %):
-            // 0.35 against 0.10.  The fine filter of a 20 M key range is 156 KB: ONE 1024-thread workgroup per CU instead of four of 512 — taken
-            // when the coarse one would pass more than a quarter of the probes; where the fine filter itself fits 40 KB it simply replaces the
-            // coarse one.  Option join_coarse_fine (default 1).
-            uint32_t shift = 6;
-            uint64_t cwords = (uint64_t) (range0 / 64 / 32) + 1;
-            const double density = range0 > 0 ? (double) back[2] / (double) range0 : 1.0;
-            const double pass64 = 1.0 - pow(1.0 - density, 64.0), pass16 = 1.0 - pow(1.0 - density, 16.0);
-            const bool coarse_on = ldb_option("join_coarse", 1) != 0;
-            bool want = coarse_on && cwords * 4 <= 40 * 1024 && (unsigned __int128) back[2] * 64 * 2 <= range0;
-            if (coarse_on && ldb_option("join_coarse_fine", 1) != 0 && pass16 <= 0.7) {
-               const uint64_t fine_words = (uint64_t) (range0 / 16 / 32) + 1;
-               const bool small = fine_words * 4 <= 40 * 1024;
-               if (small || (fine_words * 4 <= 156 * 1024 && (!want || pass64 > 0.25))) {
-                  shift = 4;
-                  cwords = fine_words;
-                  want = true;
-               }
-            }
-            // … and where a still finer one fits beside the tile kernels' queue (<= 16 KB: a supplier-sized key range), the finest that does: Q21's 4 %
-            // of the 1 M supplier keys pass 48 % of the probes at 16 keys per bit, 28 % at 8; Q7's 8 %: 74 → 49 %.  (0 = the presence bits themselves.)
-            if (coarse_on && ldb_option("join_coarse_finest", 1) != 0 && want && shift == 4 && cwords * 4 <= 16 * 1024) {
-               while (shift > 0 && ((uint64_t) (range0 >> (shift - 1)) / 32 + 1) * 4 <= 16 * 1024 && 1.0 - pow(1.0 - density, (double) (1u << shift)) > 0.1) shift--;
-               cwords = (uint64_t) (range0 >> shift) / 32 + 1;
-            }
-            if (want) {
-               LDB_TRY(LdbBufs::alloc_into(ctx, &ht->coarse, 4 * (size_t) cwords));
-               ht->coarse_words = (uint32_t) cwords;
-               ht->coarse_shift = shift;
-               hipLaunchKernelGGL(k_rank_coarse, dim3((unsigned) ((cwords + 255) / 256)), dim3(256), 0, ctx->stream, (const uint64_t*) tab, n_words, ht->coarse, (uint32_t) cwords, shift);
-               LDB_HIP(hipGetLastError());
-            }
-            if (!ht->rank_sorted) {
-               LDB_TRY(LdbBufs::alloc_into(ctx, &ht->next, 4 * (size_t) (build->n_rows ? build->n_rows : 1)));
-               h->next = (uint64_t) ht->next;
-               LdbDesc<DJoin> dp_desc(ctx);
-               LDB_TRY(dp_desc.upload(h, sizeof(*h)));
-               DJoin* dp = dp_desc.p;
-               hipLaunchKernelGGL(k_join_rank_perm, dim3(ldb_grid_for(ctx, build->n_rows, 256, 8)), dim3(256), 0, ctx->stream, dp);
-               LDB_HIP(hipGetLastError());
-               dp_desc.release();
-            }
-         } else { // duplicate keys: the promise does not hold — the general layouts below
-            LdbBufs::drop(ctx, &ht->slots);
-            h->direct = 0;
-            h->slots = 0;
-            h->counter = 0;
-            ht->unique = 0;
-            build_unique = 0;
-         }
-         dr_desc.release();
-         LDB_TRY(ldb_counters(ctx, 1, (uint64_t**) &dflags)); // (the passes below start from clean flags)
-         h->flags = (uint64_t) dflags;
-      }
-      if (ranked) {
+   JoinBuild b{ctx, build, ht.get(), h, n_keys, build_unique};
+   LDB_TRY(b.fresh_flags());
+   // KEY32: direct, rank-bitmap or ordered slots — all need the build key range first
+   if (ht->key32 && ldb_option("join_ordered", 1) != 0 && build->n_rows > 0) {
+      LDB_TRY(b.key_range(keys));
+      bool built = false;
+      LDB_TRY(b.build_rank(&built));
+      if (built) {
          *out = ht.release();
          return LDB_OK;
       }
-      if (range0 > 0 && ldb_option("join_direct", 1) != 0 && range0 <= (unsigned __int128) std::max<int64_t>(1024, 8 * build->n_rows) && range0 < ((unsigned __int128) 1 << 31) &&
-          got[0] >= INT32_MIN && got[1] <= INT32_MAX) {
-         ht->direct = 1;
-         ht->kmin = got[0];
-         ht->kmax = got[1];
-         ht->cap = (uint64_t) range0;
-         if (range0 <= ((unsigned __int128) 1 << 27) && range0 >= 4096) { // key bits: 32x smaller than the table, L2-resident for selective builds
-            const size_t words = (size_t) ((range0 + 31) / 32);
-            LDB_TRY(LdbBufs::alloc_into(ctx, &ht->key_bits, 4 * words));
-            LDB_HIP(hipMemsetAsync(ht->key_bits, 0, 4 * words, ctx->stream));
-         }
-      } else if (got[0] <= got[1]) { // at least one non-NULL key
-         ht->ordered_slots = 1;
-         ht->kmin = got[0];
-         ht->kmax = got[1];
-         ht->kmult = (uint64_t) ((((unsigned __int128) ht->cap) << 32) / ((unsigned __int128) (got[1] - got[0]) + 1));
-         {
-            // 32-bit slot arithmetic: slot = mulhi32((key - kmin) << ksh, kmult32) with (range << ksh) in [cap, 2 cap)
-            const unsigned __int128 range128 = (unsigned __int128) ((__int128) got[1] - got[0]) + 1;
-            if (ht->cap <= (1ull << 31) && range128 <= ((unsigned __int128) 1 << 32) && got[0] >= INT32_MIN && got[1] <= INT32_MAX) {
-               uint64_t range = (uint64_t) range128;
-               uint32_t ksh = 0;
-               while ((range << ksh) < ht->cap) ksh++;
-               const unsigned __int128 km = (((unsigned __int128) ht->cap) << 32) / (unsigned __int128) (range << ksh);
-               ht->kmult32 = km > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t) km;
-               ht->ksh = ksh;
-               ht->slot32 = 1;
-            }
-         }
-         // one bit per key value when that fits the L2 comfortably (DJoin::has_key_bits)
-         const unsigned __int128 range = (unsigned __int128) ((__int128) got[1] - got[0]) + 1;
-         if (range <= ((unsigned __int128) 1 << 27)) { // <= 16 MB of bits
-            const size_t words = (size_t) ((range + 31) / 32);
-            LDB_TRY(LdbBufs::alloc_into(ctx, &ht->key_bits, 4 * words));
-            LDB_HIP(hipMemsetAsync(ht->key_bits, 0, 4 * words, ctx->stream));
-         }
-      }
    }
-   // up to three passes: ordered slots → hashed slots (skewed key range) → chained (a key repeats so
-   // often that one slot per row gives long runs); each pass stops early when it sees such a run
-   const bool force_chained = ldb_option("join_chained", 0) == 1; // tests
-   if (force_chained && !ht->direct) {
-      ht->ordered_slots = 0;
-      LdbBufs::drop(ctx, &ht->key_bits);
-   }
-   if (force_chained || (ht->direct && !build_unique)) { // a direct table without the promise of unique keys chains from the start
-      ht->chained = 1;
-      LDB_TRY(LdbBufs::alloc_into(ctx, &ht->next, 4 * (size_t) (build->n_rows ? build->n_rows : 1)));
-   }
-   // two 4-byte integer keys, open addressing: the key values live in the slot (DJoin::pair32)
-   if (!ht->direct && !ht->chained && n_keys == 2 && ldb_option("join_pair32", 1) != 0) {
-      bool narrow = true;
-      for (int k = 0; k < 2; k++) {
-         const DCol& c = h->bkeys.cols[k];
-         narrow = narrow && c.width == 4 && (c.type == LDB_T_INT32 || c.type == LDB_T_DATE32 || c.type == LDB_T_CHAR4);
-      }
-      ht->pair32 = narrow ? 1 : 0;
-   }
-   ht->slot_bytes = (ht->direct ? 4 : ht->pair32 ? 16 : 8) * (size_t) ht->cap;
-   LDB_TRY(LdbBufs::alloc_into(ctx, &ht->slots, ht->slot_bytes));
-   LDB_HIP(hipMemsetAsync(ht->slots, 0, ht->slot_bytes, ctx->stream));
-   h->cap = ht->cap;
-   h->slots = (uint64_t) ht->slots;
-   for (int attempt = 0; attempt < 3; attempt++) {
-      h->direct = ht->direct;
-      h->ordered_slots = ht->ordered_slots;
-      h->kmin = ht->kmin;
-      h->kmax = ht->kmax;
-      h->kmult = ht->kmult;
-      h->kmult32 = ht->kmult32;
-      h->ksh = ht->ksh;
-      h->slot32 = ht->ordered_slots ? ht->slot32 : 0;
-      h->key_bits = (uint64_t) ht->key_bits;
-      h->has_key_bits = ht->key_bits ? 1 : 0;
-      h->chained = ht->chained;
-      h->next = (uint64_t) ht->next;
-      if (ht->chained) ht->pair32 = 0; // (a chained rebuild uses the first cap words of the same allocation)
-      h->pair32 = ht->pair32;
-      LdbDesc<DJoin> d_desc(ctx);
-      LDB_TRY(d_desc.upload(h, sizeof(*h)));
-      DJoin* d = d_desc.p;
-      if (build->n_rows && h->has_key_bits && (h->ordered_slots || h->direct)) hipLaunchKernelGGL(k_join_key_bits, dim3(ldb_grid_for(ctx, build->n_rows, 256, 8)), dim3(256), 0, ctx->stream, d);
-      if (build->n_rows) LDB_TRY(launch_join(ctx, h, d, ldb_grid_for(ctx, build->n_rows, 256, 8), "k_join_build", "k_join_build_spec", k_join_build));
-      d_desc.release();
-      uint64_t f = 0;
-      // open addressing: which insertion meets a long run depends on the order the insertions happen in, but whether ANY does is in practice
-      // a property of the keys (a run of 512 needs hundreds of equal or colliding keys: then some insertion walks it in every order).  The
-      // flag is replayed like any count — round 4 read it for real in every execution, one stream wait in the middle of every plan with an
-      // open-addressing build (Q18: 11.5 of 13.8 ms of host time blocked in this call) — and a run that does come out differently is caught
-      // by the comparison at the trace's end like any other mis-speculation: the execution is void (an insertion that gave up dropped its row)
-      // and is repeated.  Such repeats are counted apart (LDB_RB_ORDER_DEPENDENT → ldb_gpu_order_dependent_misses, bench.py's prepared_plans
-      // block): a key distribution that sits on the run-length threshold shows there instead of hiding among data-dependent misses
-      LDB_TRY(ldb_read_u64_at(ctx, dflags, &f, LDB_SITE, LDB_RB_ORDER_DEPENDENT));
-      if (ht->direct && (f & 1) && !ht->chained) { // duplicate keys in a direct table: chain them
-         ht->chained = 1;
-         LDB_TRY(LdbBufs::alloc_into(ctx, &ht->next, 4 * (size_t) build->n_rows));
-         LDB_HIP(hipMemsetAsync(ht->slots, 0, ht->slot_bytes, ctx->stream));
-         LDB_TRY(ldb_counters(ctx, 1, (uint64_t**) &dflags));
-         h->flags = (uint64_t) dflags;
-         continue;
-      }
-      if ((f & 2) && !ht->chained) {
-         if (ht->ordered_slots) { // this key distribution needs hashed slots
-            ht->ordered_slots = 0;
-            LdbBufs::drop(ctx, &ht->key_bits);
-         } else { // hashed and still long runs: duplicates → chain them
-            ht->chained = 1;
-            LDB_TRY(LdbBufs::alloc_into(ctx, &ht->next, 4 * (size_t) build->n_rows));
-         }
-         LDB_HIP(hipMemsetAsync(ht->slots, 0, ht->slot_bytes, ctx->stream));
-         LDB_TRY(ldb_counters(ctx, 1, (uint64_t**) &dflags));
-         h->flags = (uint64_t) dflags;
-         continue;
-      }
-      // the caller's promise of unique keys is verified: duplicates fall back to the general probe
-      if ((f & 1) || ht->chained) ht->unique = 0;
-      break;
-   }
+   LDB_TRY(b.choose_slots()); // (without a key range: hashed slots)
+   LDB_TRY(b.insert());
    *out = ht.release();
    return LDB_OK;
 }
@@ -942,32 +948,13 @@ static int32_t make_probe_desc(ldb_hashtable* ht, ldb_rel* probe, const ldb_colr
       if (wa != wb) LDB_FAIL(LDB_ERR_INVALID, "join_probe: key %d decimal width class differs (cast to a common type first)", k);
    }
    h->n_rows = (uint64_t) probe->n_rows;
-   h->cap = ht->cap;
-   h->slots = (uint64_t) ht->slots;
-   h->key32 = ht->key32;
-   h->ordered_slots = ht->ordered_slots;
-   h->direct = ht->direct;
-   h->rank_sorted = ht->rank_sorted;
-   h->kmin = ht->kmin;
-   h->kmax = ht->kmax;
-   h->kmult = ht->kmult;
-   h->kmult32 = ht->kmult32;
-   h->ksh = ht->ksh;
-   h->slot32 = ht->ordered_slots ? ht->slot32 : 0;
-   h->key_bits = (uint64_t) ht->key_bits;
-   h->has_key_bits = ht->key_bits ? 1 : 0;
-   h->chained = ht->chained;
-   h->next = (uint64_t) ht->next;
-   h->pair32 = 0;
+   ldb_ht_layout(ht, h);
+   h->rank_sorted = ht->rank_sorted; // (probe side only: the rank build fills next[] after its last pass over the keys)
+   h->pair32 = 0; // (1 or 2 on the probe side, by the PROBE's key columns; the build's insert passes know 0 / 1)
    if (ht->pair32 && !ht->chained) { // verify from the slot when the probe's key columns are 4-byte integers too, else through the rows
-      bool narrow = true;
-      for (int k = 0; k < 2; k++) {
-         const DCol& c = h->pkeys.cols[k];
-         narrow = narrow && c.width == 4 && (c.type == LDB_T_INT32 || c.type == LDB_T_DATE32 || c.type == LDB_T_CHAR4);
-      }
-      h->pair32 = narrow ? 1 : 2;
+      h->pair32 = join_pair_narrow(h->pkeys) ? 1 : 2;
    }
-   h->build_unique = (ht->unique && !ht->chained) ? 1 : 0;
+   h->build_unique = (ht->unique && !ht->chained) ? 1 : 0; // (probe side only: the promise as the build verified it)
    // a lazy probe relation brings its filter along: evaluated inside the probe kernel
    h->n_ppreds = (int32_t) probe->pending.size();
    // (the staging costs every workgroup the filter's bytes in loads: large probes only.  A probe with a fused filter runs the tile kernels — 256-thread
@@ -1235,7 +1222,7 @@ static int32_t probe_unique(ldb_ctx* ctx, ldb_hashtable* ht, ldb_rel* probe, Pro
    if (kind != LDB_JOIN_INNER) { // LEFT_OUTER / SINGLE: exactly one output row per probe row
       uint32_t* op;
       LDB_TRY(bufs.alloc(&op, 4 * (size_t) (n ? n : 1)));
-      if (n) hipLaunchKernelGGL(k_iota_u32j, dim3(pc.grid), dim3(256), 0, ctx->stream, op, (uint64_t) n);
+      if (n) hipLaunchKernelGGL(k_iota_u32, dim3(pc.grid), dim3(256), 0, ctx->stream, op, (uint64_t) n);
       return probe_hand_over(ctx, bufs, ht, probe, h, kind, op, match, (uint64_t) n, out);
    }
    uint64_t produced = 0;

@@ -121,11 +121,6 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_scan_expand(const uint64_t* __re
    }
 }
 
-// compose: new_rowids[j] = old_rowids[sel[j]] (sides that already had row ids)
-__global__ void k_compose(const uint32_t* __restrict__ old_rows, const uint32_t* __restrict__ sel, uint32_t* __restrict__ out, uint64_t n) {
-   for (uint64_t i = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x; i < n; i += (uint64_t) gridDim.x * blockDim.x) out[i] = old_rows[sel[i]];
-}
-
 static int32_t build_scan_desc(ldb_rel* in, const ldb_filter_desc* preds, int32_t n_preds, DScan* h) {
    if (n_preds < 0 || n_preds > LDB_MAX_PREDS) LDB_FAIL(LDB_ERR_UNSUPPORTED, "scan: %d predicates (max %d)", n_preds, LDB_MAX_PREDS);
    memset(h, 0, sizeof(*h));

@@ -25,8 +25,6 @@
 #include <memory>
 #include <vector>
 
-int32_t ldb_rel_select(ldb_ctx* ctx, ldb_rel* in, uint32_t* sel, int64_t n_sel, ldb_rel** out);
-
 // ================================================================== concatenation of two tables (same schema)
 __global__ void k_concat_offsets(const int64_t* __restrict__ a, uint64_t na, const int64_t* __restrict__ b, uint64_t nb, int64_t* __restrict__ out) {
    const uint64_t n = na + nb;
@@ -359,10 +357,6 @@ __global__ void k_win_pack_validity(const uint8_t* __restrict__ bytes, uint64_t 
    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off);
    if ((threadIdx.x & 63) == 0 && c) atomicAdd(nulls, c);
 }
-
-__global__ void k_window_iota(uint32_t* out, uint64_t n) {
-   for (uint64_t i = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x; i < n; i += (uint64_t) gridDim.x * blockDim.x) out[i] = (uint32_t) i;
-}
 extern "C" int32_t ldb_gpu_window(ldb_ctx* ctx, ldb_rel* in, const ldb_colref* part_keys, int32_t n_part, const ldb_sort_spec* order, int32_t n_order, int64_t frame_from,
                                   int64_t frame_to, const ldb_window_fn* fns, int32_t n_fns, ldb_rel** out_rel, ldb_table** out_cols) {
    if (!ctx || !in || !out_rel || !out_cols || n_part < 0 || n_order < 0 || n_fns < 1 || n_fns > LDB_WIN_MAX_FNS || !fns || n_part > LDB_MAX_KEYS)
@@ -380,7 +374,7 @@ extern "C" int32_t ldb_gpu_window(ldb_ctx* ctx, ldb_rel* in, const ldb_colref* p
       LdbBufs ib(ctx);
       uint32_t* iota;
       LDB_TRY(ib.alloc(&iota, 4 * (size_t) (in->n_rows ? in->n_rows : 1)));
-      if (in->n_rows) hipLaunchKernelGGL(k_window_iota, dim3(ldb_grid_for(ctx, in->n_rows, 256, 8)), dim3(256), 0, ctx->stream, iota, (uint64_t) in->n_rows);
+      if (in->n_rows) hipLaunchKernelGGL(k_iota_u32, dim3(ldb_grid_for(ctx, in->n_rows, 256, 8)), dim3(256), 0, ctx->stream, iota, (uint64_t) in->n_rows);
       LDB_HIP(hipGetLastError());
       ib.keep(iota); // ldb_rel_select takes the vector over
       LDB_TRY(ldb_rel_select(ctx, in, iota, in->n_rows, &sorted.r));

@@ -118,16 +118,10 @@ __global__ void k_str_maxlen(DCol col, uint64_t n, unsigned long long* out) {
    }
    if (m) atomicMax(out, m);
 }
-__global__ void k_iota(uint32_t* out, uint64_t n) {
-   for (uint64_t i = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x; i < n; i += (uint64_t) gridDim.x * blockDim.x) out[i] = (uint32_t) i;
-}
 __global__ void k_all_valid(DCol col, uint64_t n, unsigned int* flag) {
    for (uint64_t i = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x; i < n; i += (uint64_t) gridDim.x * blockDim.x)
       if (!d_valid(col, d_phys_row(col, i))) atomicOr(flag, 1u);
 }
-
-int32_t ldb_rel_select(ldb_ctx* ctx, ldb_rel* in, uint32_t* sel, int64_t n_sel, ldb_rel** out);
-int32_t ldb_gather_column(ldb_ctx* ctx, const ldb_rel* r, ldb_colref ref, ldb_column* out);
 
 // stable LSD sort of `perm` (n entries) by `words`-word records, digits [bit_lo, bit_hi) of each word
 // `varmask` (host, one word per record word, may be NULL): bits that differ between some two
@@ -382,7 +376,7 @@ static int32_t sort_records(ldb_ctx* ctx, const uint64_t* keys, int words, uint6
       LDB_HIP(hipGetLastError());
    } else {
       LDB_TRY(own.alloc(&perm, 4 * (size_t) (n ? n : 1)));
-      if (n) hipLaunchKernelGGL(k_iota, dim3(grid), dim3(256), 0, ctx->stream, perm, n);
+      if (n) hipLaunchKernelGGL(k_iota_u32, dim3(grid), dim3(256), 0, ctx->stream, perm, n);
    }
    if (m > 1 && m <= SS_MAX) hipLaunchKernelGGL(k_small_sort, dim3(1), dim3(SS_BLOCK), 0, ctx->stream, keys, words, perm, (uint32_t) m);
    else LDB_TRY(radix_sort_perm(ctx, own, keys, words, &perm, m, 0, words - 1, 0, 64, varmask.data()));
@@ -501,7 +495,7 @@ extern "C" int32_t ldb_gpu_partition(ldb_ctx* ctx, ldb_rel* in, const ldb_colref
    if (n) {
       hipLaunchKernelGGL(k_part_ids, dim3(grid), dim3(256), 0, ctx->stream, dk, n, (uint32_t) nparts, ids);
       hipLaunchKernelGGL(k_part_hist, dim3(grid), dim3(256), 0, ctx->stream, ids, n, hist);
-      hipLaunchKernelGGL(k_iota, dim3(grid), dim3(256), 0, ctx->stream, perm, n);
+      hipLaunchKernelGGL(k_iota_u32, dim3(grid), dim3(256), 0, ctx->stream, perm, n);
    }
    LDB_HIP(hipGetLastError());
    // stable counting sort on the partition id (<= 8 bits → two 4-bit passes)
