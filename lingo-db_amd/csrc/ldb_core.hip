@@ -5,6 +5,7 @@
 #include "ldb_internal.h"
 #include "ldb_device.h"
 #include "ldb_chain.h"
+#include "ldb_expand.h"
 #include <algorithm>
 #include <cstdlib>
 #include <memory>
@@ -42,7 +43,7 @@ int64_t ldb_option(const char* name, int64_t dflt) {
 }
 extern "C" int32_t ldb_gpu_set_option(const char* name, int64_t value) {
    if (!name) LDB_FAIL(LDB_ERR_INVALID, "set_option: NULL name");
-   static const char* known[] = {"jit", "jit_min_rows", "lazy_filter", "lazy_min_rows", "join_ordered", "join_chained", "gb_ordered", "gb_sorted", "zone_maps", "zone_min_rows", "gb_direct", "gb_wgs_per_cu", "gb_partition", "gb_partition_min_rows", "join_radix", "join_radix_min_rows", "join_radix_min_table_bytes", "join_radix_part_bytes", "probe_batch", "debug_check", "join_direct", "join_rank", "join_coarse", "dict_encode", "dict_min_rows", "comm_transport", "comm_timeout_ms", "desc_cache", "desc_cache_mb", "plan_replay", "scan_single_pass", "lazy_strings", "lazy_strings_min_rows", "gb_partition_wc", "join_radix_wc", "join_radix_lds", "gb_dense_out", "gb_partition_values", "join_pair32", "gb_dense_keys", "jit_async", "jit_threads", "jit_disk_cache", "join_all_match", "topk_short_select", "gb_fits64", "join_coarse_fine", "join_coarse_filtered", "compact_wide_tiles", "compact_max_words", "join_fuse_max_conjuncts", "join_coarse_finest", "jit_min_rows_like", "scan_split", "jit_share_compiles", "scan_strset_min_in"};
+   static const char* known[] = {"jit", "jit_min_rows", "lazy_filter", "lazy_min_rows", "join_ordered", "join_chained", "gb_ordered", "gb_sorted", "zone_maps", "zone_min_rows", "gb_direct", "gb_wgs_per_cu", "gb_partition", "gb_partition_min_rows", "join_radix", "join_radix_min_rows", "join_radix_min_table_bytes", "join_radix_part_bytes", "probe_batch", "debug_check", "join_direct", "join_rank", "join_coarse", "dict_encode", "dict_min_rows", "comm_transport", "comm_timeout_ms", "desc_cache", "desc_cache_mb", "plan_replay", "scan_single_pass", "lazy_strings", "lazy_strings_min_rows", "gb_partition_wc", "join_radix_wc", "join_radix_lds", "gb_dense_out", "gb_partition_values", "join_pair32", "gb_dense_keys", "jit_async", "jit_threads", "jit_disk_cache", "join_all_match", "topk_short_select", "gb_fits64", "join_coarse_fine", "join_coarse_filtered", "compact_wide_tiles", "compact_max_words", "join_fuse_max_conjuncts", "join_coarse_finest", "jit_min_rows_like", "scan_split", "jit_share_compiles", "scan_strset_min_in", "scan_expand_tiles", "scan_expand_zones", "expand_direct_pct"};
    bool ok = false;
    for (const char* k : known) ok |= strcmp(k, name) == 0;
    if (!ok) LDB_FAIL(LDB_ERR_INVALID, "set_option: unknown option '%s'", name);
@@ -2164,101 +2165,38 @@ int32_t ldb_exclusive_scan_i64(ldb_ctx* ctx, const int64_t* d_in, int64_t* d_out
 // ---------------------------------------------------------------- bitmap → ascending row numbers, one launch
 // A selection bitmap (one bit per row: ballot words of a probe / filter kernel) becomes the ascending list of set positions:
 // popcount, chained scan (above) and expansion in ONE kernel — the word_pop + scan + expand sequence it replaces was five to
-// seven launches and two temporaries per join.  A tile is 512 words (32 768 rows).  Dense tiles expand a word per wave
-// iteration (the lanes whose bit is set write one coalesced run), sparse tiles a word per lane.  With `match` the kernel also
-// writes second[j] = match[row] (the build row of a unique-key join's j-th result pair).  Entries [total, cap) are filled
-// with row 0, so that a consumer that was sized from a REPLAYED count (ldb_readback) never meets an uninitialised row id.
-// (a tile of 512 words = 32 768 rows, two words per thread: the word-per-wave expansion of a dense tile is then 128 dependent
-// steps per wave instead of 512 — a compaction over few tiles runs at that latency)
-// (round 6: two words per thread only where the bitmap is short.  A tile costs a fixed latency — ticket, loads, block scan, look-back — whatever
-// it holds: the 18 311 tiles of a 600 M-row bitmap took 16 – 27 ns each, 0.3 – 0.5 ms where its 75 MB + the row ids written are 0.05 ms of
-// traffic.  Bitmaps of >= 2 048 larger tiles take four or eight words per thread.)
+// seven launches and two temporaries per join.  A tile is 256 * BC_ITEMS words; its words and their offsets inside the tile
+// go to LDS and are expanded by d_expand_tile (ldb_expand.h: row ids staged in LDS, then streamed out coalesced) — the same
+// path at every density.  With `match` the kernel also writes second[j] = match[row] (the build row of a unique-key join's
+// j-th result pair).  Entries [total, cap) are filled with row 0, so that a consumer that was sized from a REPLAYED count
+// (ldb_readback) never meets an uninitialised row id.
+// (the offsets are tile-local, so they are written before the look-back: the wait for the predecessors covers no work of the tile's own)
+// (tile widths: ldb_bitmap_compact below)
 template <int BC_ITEMS>
 __global__ __launch_bounds__(256) void k_bitmap_compact(const uint64_t* __restrict__ bitmap, uint64_t n_words, uint64_t n_tiles, uint32_t* __restrict__ out, uint64_t cap,
                                                         const uint32_t* __restrict__ match, uint32_t* __restrict__ second, unsigned long long* __restrict__ total,
                                                         unsigned long long* __restrict__ status, unsigned long long* __restrict__ ticket, unsigned long long ticket_base,
-                                                        unsigned long long epoch) {
+                                                        unsigned long long epoch, uint32_t direct_min) {
    __shared__ unsigned long long s_tile;
    __shared__ uint32_t s_wave[4];
    __shared__ uint32_t s_prefix;
    constexpr uint32_t BC_TILE = 256 * BC_ITEMS;
-   __shared__ uint32_t s_off[BC_TILE];
-   __shared__ uint64_t s_words[BC_TILE]; // the tile's words for the word-per-wave expansion (a wave re-reading them from memory one by
-                                            // one runs at memory latency: 512 dependent round trips per wave)
+   __shared__ __attribute__((aligned(16))) unsigned char s_lds[EXPAND_LDS_BYTES(BC_ITEMS)];
    if (threadIdx.x == 0) s_tile = atomicAdd(ticket, 1ull) - ticket_base;
    __syncthreads();
    const uint64_t tile = s_tile;
    const uint64_t word0 = tile * BC_TILE;
-   // word w of the tile is handled by thread w % 256 in round w / 256 (coalesced loads); offsets go through LDS
-   uint64_t m[BC_ITEMS];
-   uint32_t cnt[BC_ITEMS];
-   uint32_t sum = 0;
-#pragma unroll
-   for (int k = 0; k < BC_ITEMS; k++) {
-      const uint64_t w = word0 + (uint64_t) k * 256 + threadIdx.x;
-      m[k] = w < n_words ? bitmap[w] : 0;
-      cnt[k] = (uint32_t) __popcll(m[k]);
-      s_off[k * 256 + threadIdx.x] = cnt[k];
-      s_words[k * 256 + threadIdx.x] = m[k];
-   }
-   __syncthreads();
-   // thread t scans words [8t, 8t + 8) of the tile (consecutive words → consecutive output positions)
-   uint32_t own[BC_ITEMS];
-#pragma unroll
-   for (int k = 0; k < BC_ITEMS; k++) {
-      own[k] = s_off[threadIdx.x * BC_ITEMS + k];
-      sum += own[k];
-   }
-   uint32_t agg;
-   uint32_t excl = d_block_scan256<uint32_t>(sum, s_wave, &agg);
+   const uint32_t agg = d_expand_load_scan<BC_ITEMS>(bitmap, word0, n_words, s_lds, s_wave);
    if (threadIdx.x < 64) {
       const uint32_t prefix = d_chain_prefix<uint32_t, 32>(status, tile, epoch, agg, threadIdx.x);
       if (threadIdx.x == 0) s_prefix = prefix;
    }
    __syncthreads();
    const uint32_t tile_base = s_prefix;
-   excl += tile_base;
-#pragma unroll
-   for (int k = 0; k < BC_ITEMS; k++) {
-      s_off[threadIdx.x * BC_ITEMS + k] = excl;
-      excl += own[k];
-   }
    if (tile == n_tiles - 1 && threadIdx.x == 0) {
       if (total) *total = (unsigned long long) tile_base + agg;
    }
-   __syncthreads();
-   if (agg * 8u < BC_TILE * 64u) { // fewer than one set bit in eight: a word per lane
-#pragma unroll
-      for (int k = 0; k < BC_ITEMS; k++) {
-         uint64_t mm = m[k];
-         if (!mm) continue;
-         uint32_t at = s_off[k * 256 + threadIdx.x];
-         const uint32_t base = (uint32_t) ((word0 + (uint64_t) k * 256 + threadIdx.x) * 64);
-         while (mm) {
-            const uint32_t row = base + (uint32_t) __builtin_ctzll(mm);
-            if (at < cap) { // (cap < the real count only under a wrong replayed count: never write past the buffer)
-               out[at] = row;
-               if (match) second[at] = match[row];
-            }
-            at++;
-            mm &= mm - 1;
-         }
-      }
-   } else { // a word per wave iteration
-      const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-      for (uint32_t w = wave; w < BC_TILE; w += 4) {
-         if (word0 + w >= n_words) break;
-         const uint64_t mm = s_words[w]; // wave-uniform
-         if ((mm >> lane) & 1) {
-            const uint32_t at = s_off[w] + d_rank_in(mm);
-            const uint32_t row = (uint32_t) ((word0 + w) * 64 + lane);
-            if (at < cap) {
-               out[at] = row;
-               if (match) second[at] = match[row];
-            }
-         }
-      }
-   }
+   d_expand_tile<BC_ITEMS>(s_lds, agg, direct_min, (uint32_t) (word0 * 64), tile_base, out, cap, match, second);
    if (tile == n_tiles - 1) { // the tail behind the real count (see above)
       const uint64_t end = (uint64_t) tile_base + agg;
       for (uint64_t i = end + threadIdx.x; i < cap; i += 256) {
@@ -2272,6 +2210,9 @@ int32_t ldb_bitmap_compact(ldb_ctx* ctx, const uint64_t* bitmap, int64_t n_words
       if (d_total) LDB_HIP(hipMemsetAsync(d_total, 0, 8, ctx->stream));
       return LDB_OK;
    }
+   // two words per thread where the bitmap is short, four or eight from 2 048 larger tiles on: a tile costs a fixed latency (ticket, loads, block scan,
+   // look-back) whatever it holds.  Measured again with the staged expansion (256 M rows, profiles/expand_sweep.json): eight words win below 5 % set
+   // (46 against 71 and 114 µs at 0.1 %), four from 50 % on (441 against 514 µs); joins compact a few per cent, so the defaults stand.
    const int64_t wide = ldb_option("compact_wide_tiles", 1); // 0 = two words per thread always, 1 = the default floor of 2 048 tiles, n > 1 = that floor
    const int64_t floor_tiles = wide > 1 ? wide : 2048;
    const int64_t most = ldb_option("compact_max_words", 8);
@@ -2282,7 +2223,7 @@ int32_t ldb_bitmap_compact(ldb_ctx* ctx, const uint64_t* bitmap, int64_t n_words
    LdbProf prof_(ctx, "k_bitmap_compact");
 #define LDB_BC_LAUNCH(I) \
    hipLaunchKernelGGL(k_bitmap_compact<I>, dim3((unsigned) n_tiles), dim3(256), 0, ctx->stream, bitmap, (uint64_t) n_words, n_tiles, out, cap, match, second, (unsigned long long*) d_total, c.status, \
-                      c.ticket, c.ticket_base, c.epoch)
+                      c.ticket, c.ticket_base, c.epoch, ldb_expand_direct_min(I, match != nullptr))
    if (items == 16) LDB_BC_LAUNCH(16);
    else if (items == 8) LDB_BC_LAUNCH(8);
    else if (items == 4) LDB_BC_LAUNCH(4);

@@ -6,9 +6,10 @@
 // predicate.  Here one pass evaluates the whole conjunction per row (later conjuncts only load
 // their column for lanes still alive), a wave turns its 64 verdicts into one 64-bit ballot word,
 // and the selection is produced from that bitmap (1 bit/row of extra traffic) in ascending row
-// order: k_scan_bitmap → block-count scan → k_scan_expand (mbcnt rank → coalesced id writes).
+// order: k_scan_bitmap → block-count scan → k_scan_expand (row ids staged in LDS → coalesced id writes).
 #include "ldb_internal.h"
 #include "ldb_device.h"
+#include "ldb_expand.h"
 #include <memory>
 
 #include "ldb_scan_kernel.h"
@@ -84,41 +85,24 @@ bool ldb_scan_jit_check(std::string* log) {
    return ldb_jit_compile_only("ldb_scan_kernel.h", "DScanDnf", DNF_SPEC_SRC, dn.get(), sizeof(DScanDnf), log);
 }
 
-// Expand the bitmap into ascending row ids.  Each wave walks its words; the lane whose bit is
-// set writes its row id at block_offset + (#set bits in earlier words) + rank within the word.
-__global__ __launch_bounds__(SCAN_BLOCK) void k_scan_expand(const uint64_t* __restrict__ bitmap, const uint32_t* __restrict__ block_offsets,
-                                                            uint32_t* __restrict__ out_rows, uint64_t n_rows, uint64_t cap, uint32_t parts) {
-   __shared__ uint32_t s_pop[SCAN_WORDS_PER_BLOCK];
-   const uint64_t word0 = (uint64_t) blockIdx.x * SCAN_WORDS_PER_BLOCK;
-   const uint64_t n_words = (n_rows + 63) / 64;
-   uint64_t my = word0 + threadIdx.x < n_words ? bitmap[word0 + threadIdx.x] : 0;
-   s_pop[threadIdx.x] = (uint32_t) __popcll(my);
+// Expand the bitmap into ascending row ids.  A workgroup owns ZONES consecutive zones of 256 words (long inputs: fewer, larger tiles): it
+// loads their words into LDS once, scans the popcounts and expands through d_expand_tile (ldb_expand.h), as k_bitmap_compact does; its
+// base is the first zone's offset from the count scan (the zones are consecutive, so the offsets inside the tile follow from it).
+template <int ZONES>
+__global__ __launch_bounds__(SCAN_BLOCK) void k_scan_expand(const uint64_t* __restrict__ bitmap, const uint32_t* __restrict__ block_offsets, uint32_t* __restrict__ out_rows, uint64_t n_rows,
+                                                            uint64_t cap, uint32_t parts, uint32_t direct_min) {
+   constexpr uint32_t TILE = SCAN_WORDS_PER_BLOCK * ZONES;
+   __shared__ uint32_t s_wave[4];
+   __shared__ __attribute__((aligned(16))) unsigned char s_lds[EXPAND_LDS_BYTES(ZONES)];
+   const uint64_t word0 = (uint64_t) blockIdx.x * TILE;
+   const uint32_t total = d_expand_load_scan<ZONES>(bitmap, word0, (n_rows + 63) / 64, s_lds, s_wave);
    __syncthreads();
-   // exclusive scan over the 256 word popcounts (Hillis-Steele in LDS)
-   uint32_t own = s_pop[threadIdx.x];
-   for (int off = 1; off < SCAN_WORDS_PER_BLOCK; off <<= 1) {
-      uint32_t t = threadIdx.x >= (unsigned) off ? s_pop[threadIdx.x - off] : 0;
-      __syncthreads();
-      s_pop[threadIdx.x] += t;
-      __syncthreads();
-   }
-   uint32_t excl = s_pop[threadIdx.x] - own;
-   const uint32_t block_total = s_pop[SCAN_WORDS_PER_BLOCK - 1];
-   __syncthreads();
-   s_pop[threadIdx.x] = excl;
-   __syncthreads();
-   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-   const uint32_t base = block_offsets[blockIdx.x * parts]; // (the scan kernels count per part of a zone: the first part's offset is the zone's)
+   const uint32_t base = block_offsets[(uint64_t) blockIdx.x * ZONES * parts]; // (the scan kernels count per part of a zone: the first part's offset is the zone's)
+   d_expand_tile<ZONES>(s_lds, total, direct_min, (uint32_t) (word0 * 64), base, out_rows, cap, nullptr, nullptr); // (cap = the host's count; see ldb_readback)
    // entries behind the real count (cap is larger only when it came from a replayed count that no longer holds) must
    // still be row numbers: the consumer is already queued
    if (blockIdx.x == gridDim.x - 1)
-      for (uint64_t i = (uint64_t) base + block_total + threadIdx.x; i < cap; i += SCAN_BLOCK) out_rows[i] = 0;
-   for (uint32_t w = wave; w < SCAN_WORDS_PER_BLOCK; w += SCAN_BLOCK / LDB_WAVE) {
-      if (word0 + w >= n_words) break;
-      uint64_t m = bitmap[word0 + w]; // wave-uniform
-      const uint64_t at = (uint64_t) base + s_pop[w] + d_rank_in(m);
-      if (((m >> lane) & 1) && at < cap) out_rows[at] = (uint32_t) ((word0 + w) * 64 + lane); // (cap = the host's count; see ldb_readback)
-   }
+      for (uint64_t i = (uint64_t) base + total + threadIdx.x; i < cap; i += SCAN_BLOCK) out_rows[i] = 0;
 }
 
 static int32_t build_scan_desc(ldb_rel* in, const ldb_filter_desc* preds, int32_t n_preds, DScan* h) {
@@ -192,7 +176,20 @@ static int32_t scan_run_with(ldb_ctx* ctx, int64_t n, LAUNCH launch, uint32_t** 
    // the whole execution at the final comparison: 7 of the 22 queries paid that once during warm-up)
    LDB_TRY(ldb_read_u64_at(ctx, d_total, &total, ldb_site_derived(LDB_SITE, (uint32_t) n), 0));
    LDB_TRY(tmp.alloc(&sel, sizeof(uint32_t) * (size_t) (total ? total : 1)));
-   if (total) hipLaunchKernelGGL(k_scan_expand, dim3((unsigned) n_blocks), dim3(SCAN_BLOCK), 0, ctx->stream, bitmap, offsets, sel, (uint64_t) n, total, (uint32_t) parts);
+   if (total) {
+      // zones per workgroup: 4 or 2 where that leaves `scan_expand_tiles` tiles (default 2 048), or exactly `scan_expand_zones` (1, 2, 4, 8) where that is set
+      // (256 M rows: four zones took 15 / 27 / 127 µs at 0.1 / 5 / 50 % set, one zone 22 / 32 / 135, eight 16 / 33 / 167: profiles/expand_sweep.json)
+      const int64_t floor_tiles = ldb_option("scan_expand_tiles", 2048), fixed = ldb_option("scan_expand_zones", 0);
+      const int zones = fixed == 1 || fixed == 2 || fixed == 4 || fixed == 8 ? (int) fixed : n_blocks >= floor_tiles * 4 ? 4 : n_blocks >= floor_tiles * 2 ? 2 : 1;
+      const unsigned n_tiles = (unsigned) ((n_blocks + zones - 1) / zones);
+#define LDB_SE_LAUNCH(Z) hipLaunchKernelGGL(k_scan_expand<Z>, dim3(n_tiles), dim3(SCAN_BLOCK), 0, ctx->stream, bitmap, offsets, sel, (uint64_t) n, total, (uint32_t) parts, \
+                                         ldb_expand_direct_min(Z, false))
+      if (zones == 8) LDB_SE_LAUNCH(8);
+      else if (zones == 4) LDB_SE_LAUNCH(4);
+      else if (zones == 2) LDB_SE_LAUNCH(2);
+      else LDB_SE_LAUNCH(1);
+#undef LDB_SE_LAUNCH
+   }
    LDB_HIP(hipGetLastError());
    tmp.keep(sel);
    *sel_out = sel;
