@@ -499,22 +499,31 @@ int32_t ldb_gpu_map_substr(ldb_ctx* ctx, ldb_rel* in, ldb_colref col, int64_t fr
  *     byte >= 0x80 passes through, so multi-byte UTF-8 characters (ß, É …) are untouched;
  *   - a window (from, for_len) on a COL part is StringRuntime::substr in CHARACTERS, exactly ldb_gpu_map_substr's, applied
  *     BEFORE the case mapping; from = 1 and for_len = LDB_STR_WHOLE take the whole string without reading it;
- *   - an INT part is StringRuntime::fromInt: plain decimal, a leading '-', no padding (INT64_MIN included).
+ *   - an INT part is StringRuntime::fromInt: plain decimal, a leading '-', no padding (INT64_MIN included);
+ *   - a DECIMAL part is StringRuntime::fromDecimal (:217-222) = arrow's Decimal128::ToString(scale) with the column's scale,
+ *     at any stored width.  With d the digits of |v|, nd their number and adj = nd - 1 - scale: a leading '-' for v < 0, then
+ *     scale = 0: d; adj < -6: the scientific form d[0], '.' and d[1:] if nd > 1, "E-" and -adj in decimal (1 at scale 8 is
+ *     "1E-8", 0 is "0E-8"); nd > scale: d with a point before its last `scale` digits; otherwise "0.", scale - nd zeros, d;
+ *   - a DATE part is StringRuntime::fromDate (:452-456, "%F"): the ten bytes YYYY-MM-DD, defined for 0001-01-01 … 9999-12-31
+ *     (day -719162 … 2932896).  A day outside (where the reference's %F changes width) makes the row NULL, so a DATE part
+ *     always makes the result nullable.
  * ldb_gpu_map_strcat gives one utf8 column: the parts of each row concatenated left to right; one COL part with
- * LDB_SC_UPPER is upper(col), one with LDB_SC_NONE a copy.  A row with a NULL in any COL / INT part is NULL; the result is
- * nullable when a COL / INT part is (a validity bitmap, or the NULL row ids of an outer join's padded side).
+ * LDB_SC_UPPER is upper(col), one with LDB_SC_NONE a copy, one INT / DECIMAL / DATE part cast(col as varchar).  A row with
+ * a NULL in any COL / INT / DECIMAL / DATE part is NULL; the result is nullable when such a part is (a validity bitmap, or
+ * the NULL row ids of an outer join's padded side).
  * Errors: n_parts < 1 or > LDB_MAX_STRPARTS is LDB_ERR_UNSUPPORTED naming the limit; a COL part over a column that is not
- * utf8, an INT part over a column that is not int32 / int64, an unknown kind / strcase, and a strcase or a window on a
- * CONST / INT part are LDB_ERR_INVALID naming the part index.  Constants may be of any length.  Offsets of the result are
- * the library's 64-bit offsets. */
+ * utf8, an INT part over a column that is not int32 / int64, a DECIMAL part over one that is not decimal128, a DATE part
+ * over one that is not date32, an unknown kind / strcase, and a strcase or a window on any part but a COL part are
+ * LDB_ERR_INVALID naming the part index.  Constants may be of any length.  Offsets of the result are the library's 64-bit
+ * offsets. */
 #define LDB_MAX_STRPARTS 8
 #define LDB_STR_WHOLE INT64_MAX /* for_len: to the end of the string */
-typedef enum { LDB_SP_COL = 0, LDB_SP_CONST = 1, LDB_SP_INT = 2 } ldb_strpart_kind;
+typedef enum { LDB_SP_COL = 0, LDB_SP_CONST = 1, LDB_SP_INT = 2, LDB_SP_DECIMAL = 3, LDB_SP_DATE = 4 } ldb_strpart_kind;
 typedef enum { LDB_SC_NONE = 0, LDB_SC_UPPER = 1, LDB_SC_LOWER = 2 } ldb_strcase;
 typedef struct {
    int32_t kind; /* ldb_strpart_kind */
    int32_t strcase; /* ldb_strcase; COL parts only */
-   ldb_colref col; /* COL: a utf8 column; INT: an int32 / int64 column */
+   ldb_colref col; /* COL: a utf8 column; INT: an int32 / int64 column; DECIMAL: a decimal128 column; DATE: a date32 column */
    const char* str; /* CONST: bytes (need not be NUL-terminated) */
    int64_t str_len;
    int64_t from, for_len; /* COL: StringRuntime::substr window in CHARACTERS, applied before the case mapping; 1 / LDB_STR_WHOLE = the whole string */
@@ -523,6 +532,32 @@ int32_t ldb_gpu_map_strcat(ldb_ctx* ctx, ldb_rel* in, const ldb_strpart* parts, 
 /* StringRuntime::len: the number of UTF-8 characters (bytes that are not 10xxxxxx) of a utf8 column as an INT64 column;
  * NULL in → NULL out. */
 int32_t ldb_gpu_map_strlen(ldb_ctx* ctx, ldb_rel* in, ldb_colref col, const char* name, ldb_table** out);
+/* A utf8 column parsed as INT64, DECIMAL128(precision, scale) or DATE32: cast(col as int | decimal | date), the runtime calls
+ * StringRuntime::toInt (:174-185), toDecimal (:187-200) and toDate (:439-444).  The result is one NULLABLE column, a value
+ * per row of `in`.  NULL in → NULL out (validity bitmaps and the NULL row ids of an outer join's padded side).  A BAD row —
+ * a non-NULL string on which the reference throws or leaves its result undefined — is NULL too, and counted: *n_bad when
+ * n_bad is not NULL (one recorded read-back, like the total of ldb_gpu_map_strcat); with n_bad = NULL nothing is read back.
+ *   - LDB_PARSE_INT64 is std::stoll that must consume the whole string: any number of leading C-locale isspace bytes (0x20,
+ *     0x09 – 0x0D), an optional '+' or '-', at least one digit, the end.  Bad: trailing bytes, no digit, a value outside int64
+ *     (-9223372036854775808 is valid).
+ *   - LDB_PARSE_DECIMAL is arrow's Decimal128::FromString, then Rescale to `scale`: sign?, digits*, ('.' digits*)?,
+ *     ([eE] sign? digits+)? with at least one digit in front of the exponent and no white space anywhere (as in arrow, the
+ *     exponent is a '+' that is skipped and then an int32: "e+-2" is e-2).  Leading zeros are free; more than 38 significant
+ *     digits are bad, and so is an exponent that is not an int32 or that puts the parsed scale below -38 or more than 38
+ *     above `scale` (FromString refuses the one, Rescale has no multiplier for the other).  Rescaling down is bad when it would
+ *     drop a non-zero digit ("1.234" to scale 2; "1.230" is fine), rescaling up on overflow.  A result with
+ *     |v| >= 10^precision is bad: this is STRICTER than the reference, which returns a value that violates the column type,
+ *     and is the validation an imported decimal column needs (arrow's own cast does the same).
+ *   - LDB_PARSE_DATE is arrow's ParseValue<Date32Type>: exactly the ten bytes DDDD-DD-DD, a valid day of the proleptic
+ *     Gregorian calendar in the years 0001 … 9999 (the range of a DATE part above); anything else is bad — another length
+ *     (decided from the offsets alone), a non-digit, month 0 or 13, 1900-02-29, a space.
+ * precision and scale are looked at for LDB_PARSE_DECIMAL only.  Errors (LDB_ERR_INVALID, no work done): a column that is not
+ * utf8, an unknown kind, a precision outside 1 … 38, a scale outside 0 … precision.
+ * One row per lane: only a pathologically long VALID text (megabytes of leading zeros or blanks) serialises its wave, the
+ * limit this shares with ldb_gpu_map_strlen; garbage of any length costs one load. */
+typedef enum { LDB_PARSE_INT64 = 0, LDB_PARSE_DECIMAL = 1, LDB_PARSE_DATE = 2 } ldb_parse_kind;
+int32_t ldb_gpu_map_strparse(ldb_ctx* ctx, ldb_rel* in, ldb_colref col, int32_t kind, int32_t precision, int32_t scale,
+                             const char* name, ldb_table** out, int64_t* n_bad);
 /* `in` extended by a table of exactly ldb_gpu_rel_rows(in) rows as a new LAST side (identity row
  * ids); the table must outlive the relation. */
 int32_t ldb_gpu_rel_zip(ldb_ctx* ctx, ldb_rel* in, const ldb_table* t, ldb_rel** out);

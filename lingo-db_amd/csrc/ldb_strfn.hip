@@ -1,19 +1,22 @@
-// ldb_strfn.hip — string expressions as computed columns: upper / lower / || / cast(int as varchar) / length.
+// ldb_strfn.hip — string expressions as computed columns: upper / lower / || / cast(int | decimal | date as varchar) / length.
 // Replaces (reference): the runtime calls the SQL frontend emits for these (sql_mlir_translator.cpp:910-936, registered in
 // Dialect/DB/RuntimeFunctions/RuntimeFunctions.cpp:276-285) and src/runtime/StringRuntime.cpp executes per tuple:
 // toUpper / toLower (:355-364, :396-418: std::toupper / std::tolower byte by byte in the C locale — only a-z / A-Z change,
 // bytes >= 0x80 pass through), concat (:419-432: bytes of a, then bytes of b), fromInt (:201-212: arrow's StringFormatter —
-// plain decimal with a leading '-'), substr (:292-319, see ldb_strfn.h) and len (:276-290: bytes that are not 10xxxxxx).
+// plain decimal with a leading '-'), fromDecimal (:217-222) and fromDate (:452-456; both in ldb_strcast.h), substr (:292-319,
+// see ldb_strfn.h) and len (:276-290: bytes that are not 10xxxxxx).
 //
 // One result row = the PARTS of that row left to right (ldb_strpart: a utf8 column — whole or a character window, as it is
-// or case-mapped —, a constant, or an integer column as decimal text).  Three steps:
+// or case-mapped —, a constant, or an integer / decimal / date column as text).  Three steps:
 //   k_strcat_lens   one output length per row + the validity bitmap (written as 64-bit words from a wave ballot).  A whole
-//                   column part costs two offset loads, an INT part a digit count; only a windowed part reads its string,
+//                   column part costs two offset loads, an INT / DECIMAL part a digit count, a DATE part a range check; only
+//                   a windowed part reads its string,
 //                   and leaves (first byte, byte length) of the window per row for the fill.
 //   ldb_exclusive_scan_i64   lengths → 64-bit offsets.
 //   k_strcat_fill   parallel over OUTPUT BYTES: see there.
 #include "ldb_internal.h"
 #include "ldb_strfn.h"
+#include "ldb_strcast.h"
 #include <climits>
 
 struct DSPart {
@@ -66,6 +69,12 @@ __device__ __forceinline__ uint32_t d_part_len(const DSPart& p, uint64_t i, uint
       return 0;
    }
    if (p.kind == LDB_SP_INT) return d_int_text_len(d_load_i64(p.col, row));
+   if (p.kind == LDB_SP_DECIMAL) return d_dec_text_len(d_load_i128(p.col, row), p.col.scale);
+   if (p.kind == LDB_SP_DATE) { // fromDate is ten bytes inside 0001-01-01 … 9999-12-31 only: a day outside makes the row NULL
+      const int64_t day = d_load_i64(p.col, row);
+      if (day < SC_DATE_MIN || day > SC_DATE_MAX) *ok = false;
+      return SC_DATE_TEXT_LEN;
+   }
    if (!p.windowed) {
       uint32_t len;
       (void) d_load_str(p.col, row, &len);
@@ -120,34 +129,12 @@ __device__ __forceinline__ uint64_t d_swar_case(uint64_t x, int strcase) {
    const uint64_t m = (y + (0x80 - 'A') * ones) & ~(y + (0x80 - ('Z' + 1)) * ones) & ~x & high;
    return x + (m >> 2);
 }
-__device__ __forceinline__ uint64_t d_pow10_u64(uint32_t k) {
-   uint64_t r = 1;
-   for (uint32_t j = 0; j < k; j++) r *= 10;
-   return r;
-}
-
 // `seg` (1 … 16) bytes of part p on logical row i, from byte `q` of the part's text, as a little-endian 128-bit value
 __device__ __forceinline__ u128 d_part_bytes(const DStrcat& d, const DSPart& p, uint64_t i, uint64_t n, const uint32_t* __restrict__ aux, uint32_t q, uint32_t seg) {
-   if (p.kind == LDB_SP_INT) {
-      const int64_t v = d_load_i64(p.col, d_phys_row(p.col, i));
-      const uint64_t a = v < 0 ? 0 - (uint64_t) v : (uint64_t) v;
-      const uint32_t neg = v < 0 ? 1u : 0u, nd = d_dec_digits(a);
-      u128 r = 0;
-      // text byte t: '-' at t = 0 of a negative value, else digit (t - neg) from the left
-      uint64_t scale = d_pow10_u64(nd - 1 - (q > neg ? q - neg : 0));
-      for (uint32_t k = 0; k < seg; k++) {
-         const uint32_t t = q + k;
-         uint8_t c;
-         if (t < neg) {
-            c = '-';
-         } else {
-            c = (uint8_t) ('0' + (a / scale) % 10);
-            scale /= 10;
-         }
-         r |= (u128) c << (8 * k);
-      }
-      return r;
-   }
+   // the text of a number is produced once, in registers (ldb_strcast.h), and the bytes asked for are cut out of it
+   if (p.kind == LDB_SP_INT) return d_num_text_bytes(d_int_text(d_load_i64(p.col, d_phys_row(p.col, i))), q, seg);
+   if (p.kind == LDB_SP_DECIMAL) return d_num_text_bytes(d_dec_text(d_load_i128(p.col, d_phys_row(p.col, i)), p.col.scale), q, seg);
+   if (p.kind == LDB_SP_DATE) return d_date_text_bytes((int32_t) d_load_i64(p.col, d_phys_row(p.col, i)), q, seg);
    uint64_t at, avail; // first source byte in its buffer, bytes of the buffer
    const uint8_t* base;
    if (p.kind == LDB_SP_CONST) {
@@ -321,12 +308,13 @@ extern "C" int32_t ldb_gpu_map_strcat(ldb_ctx* ctx, ldb_rel* in, const ldb_strpa
    // the arguments alone first: a refused call does no work (no lazy column is written out for it)
    for (int32_t k = 0; k < n_parts; k++) {
       const ldb_strpart& p = parts[k];
-      if (p.kind != LDB_SP_COL && p.kind != LDB_SP_CONST && p.kind != LDB_SP_INT) LDB_FAIL(LDB_ERR_INVALID, "map_strcat: part %d: unknown kind %d", k, p.kind);
+      if (p.kind < LDB_SP_COL || p.kind > LDB_SP_DATE) LDB_FAIL(LDB_ERR_INVALID, "map_strcat: part %d: unknown kind %d", k, p.kind);
       if (p.strcase != LDB_SC_NONE && p.strcase != LDB_SC_UPPER && p.strcase != LDB_SC_LOWER) LDB_FAIL(LDB_ERR_INVALID, "map_strcat: part %d: unknown strcase %d", k, p.strcase);
       if (p.kind != LDB_SP_COL) {
-         if (p.strcase != LDB_SC_NONE) LDB_FAIL(LDB_ERR_INVALID, "map_strcat: part %d: a case mapping on a %s part (column parts only)", k, p.kind == LDB_SP_CONST ? "constant" : "integer");
+         const char* what = p.kind == LDB_SP_CONST ? "constant" : p.kind == LDB_SP_INT ? "integer" : p.kind == LDB_SP_DECIMAL ? "decimal" : "date";
+         if (p.strcase != LDB_SC_NONE) LDB_FAIL(LDB_ERR_INVALID, "map_strcat: part %d: a case mapping on a %s part (column parts only)", k, what);
          const bool no_window = (p.from == 0 && p.for_len == 0) || (p.from == 1 && p.for_len == LDB_STR_WHOLE);
-         if (!no_window) LDB_FAIL(LDB_ERR_INVALID, "map_strcat: part %d: a window on a %s part (column parts only)", k, p.kind == LDB_SP_CONST ? "constant" : "integer");
+         if (!no_window) LDB_FAIL(LDB_ERR_INVALID, "map_strcat: part %d: a window on a %s part (column parts only)", k, what);
       }
       if (p.kind == LDB_SP_CONST && (p.str_len < 0 || p.str_len > (int64_t) UINT32_MAX || (p.str_len > 0 && !p.str))) LDB_FAIL(LDB_ERR_INVALID, "map_strcat: part %d: bad constant (%lld bytes)", k, (long long) p.str_len);
    }
@@ -355,9 +343,11 @@ extern "C" int32_t ldb_gpu_map_strcat(ldb_ctx* ctx, ldb_rel* in, const ldb_strpa
          const int t = strfn_column(in, p.col)->type.type;
          if (p.kind == LDB_SP_COL && t != LDB_T_UTF8) LDB_FAIL(LDB_ERR_INVALID, "map_strcat: part %d: a utf8 column expected (type %d)", k, t);
          if (p.kind == LDB_SP_INT && t != LDB_T_INT32 && t != LDB_T_INT64) LDB_FAIL(LDB_ERR_INVALID, "map_strcat: part %d: an int32 / int64 column expected (type %d)", k, t);
+         if (p.kind == LDB_SP_DECIMAL && t != LDB_T_DECIMAL128) LDB_FAIL(LDB_ERR_INVALID, "map_strcat: part %d: a decimal128 column expected (type %d)", k, t);
+         if (p.kind == LDB_SP_DATE && t != LDB_T_DATE32) LDB_FAIL(LDB_ERR_INVALID, "map_strcat: part %d: a date32 column expected (type %d)", k, t);
       }
       LDB_TRY(ldb_make_dcol(in, p.col, &q.col));
-      nullable = nullable || q.col.validity || q.col.rowids;
+      nullable = nullable || q.col.validity || q.col.rowids || p.kind == LDB_SP_DATE; // (a day outside 0001 … 9999 is NULL)
       if (p.kind == LDB_SP_COL) {
          q.src_bytes = (uint64_t) std::max<int64_t>(0, strfn_column(in, p.col)->value_bytes);
          q.windowed = !(p.from == 1 && p.for_len == LDB_STR_WHOLE);

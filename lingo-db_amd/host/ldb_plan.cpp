@@ -1069,7 +1069,7 @@ struct Interp {
             check(ldb_gpu_map_strcat(ctx, in, &p, 1, as.c_str(), &t), ("map " + fn).c_str());
          } else if (fn == "length") { // StringLength: UTF-8 characters
             check(ldb_gpu_map_strlen(ctx, in, resolve(*sides, st.s("col"), "map"), as.c_str(), &t), "map length");
-         } else if (fn == "concat") { // Concatenate (flattened): constants, columns (window, case mapping), integers as text
+         } else if (fn == "concat") { // Concatenate (flattened): constants, columns (window, case mapping), integers / decimals / dates as text
             std::vector<ldb_strpart> ps;
             for (auto& e : st.at("parts").arr) {
                ldb_strpart p = {LDB_SP_CONST, LDB_SC_NONE, {0, 0}, nullptr, 0, 1, LDB_STR_WHOLE};
@@ -1079,6 +1079,12 @@ struct Interp {
                } else if (e.get("int")) {
                   p.kind = LDB_SP_INT;
                   p.col = resolve(*sides, e.s("int"), "map concat");
+               } else if (e.get("dec")) {
+                  p.kind = LDB_SP_DECIMAL;
+                  p.col = resolve(*sides, e.s("dec"), "map concat");
+               } else if (e.get("date")) {
+                  p.kind = LDB_SP_DATE;
+                  p.col = resolve(*sides, e.s("date"), "map concat");
                } else {
                   p.kind = LDB_SP_COL;
                   p.col = resolve(*sides, e.s("col"), "map concat");
@@ -1089,6 +1095,25 @@ struct Interp {
                ps.push_back(p);
             }
             check(ldb_gpu_map_strcat(ctx, in, ps.data(), (int32_t) ps.size(), as.c_str(), &t), "map concat");
+         } else if (fn == "to_varchar") { // fromInt / fromDecimal / fromDate: a one-part concat whose kind follows the column's type
+            ldb_strpart p = {LDB_SP_INT, LDB_SC_NONE, resolve(*sides, st.s("col"), "map to_varchar"), nullptr, 0, 1, LDB_STR_WHOLE};
+            ldb_coltype ct = {0, 0, 0, 0};
+            ldb_gpu_table_coltype((*sides)[(size_t) p.col.side], p.col.col, &ct);
+            if (ct.type == LDB_T_DECIMAL128) p.kind = LDB_SP_DECIMAL;
+            else if (ct.type == LDB_T_DATE32) p.kind = LDB_SP_DATE;
+            else if (ct.type != LDB_T_INT32 && ct.type != LDB_T_INT64)
+               throw std::runtime_error("map to_varchar: column '" + st.s("col") + "' of type " + std::to_string(ct.type) + " (int32 / int64, decimal128 or date32 expected)");
+            check(ldb_gpu_map_strcat(ctx, in, &p, 1, as.c_str(), &t), "map to_varchar");
+         } else if (fn == "to_int" || fn == "to_decimal" || fn == "to_date") { // toInt / toDecimal / toDate
+            const int32_t kind = fn == "to_int" ? LDB_PARSE_INT64 : fn == "to_decimal" ? LDB_PARSE_DECIMAL : LDB_PARSE_DATE;
+            const bool fail = st.sOr("on_error", "fail") == "fail"; // as the reference's throw; "null": bad rows are NULL, nothing is read back
+            int64_t bad = 0;
+            check(ldb_gpu_map_strparse(ctx, in, resolve(*sides, st.s("col"), "map"), kind, (int32_t) st.iOr("precision", 0), (int32_t) st.iOr("scale", 0), as.c_str(), &t, fail ? &bad : nullptr),
+                  ("map " + fn).c_str());
+            if (bad) {
+               ldb_gpu_table_release(ctx, t);
+               throw std::runtime_error("map " + fn + ": " + std::to_string(bad) + " bad row" + (bad == 1 ? "" : "s") + " in column '" + st.s("col") + "' (on_error: \"null\" makes them NULL)");
+            }
          } else {
             XB b;
             const Scalar ty = compileX(*sides, st.at("expr"), b);
@@ -1590,11 +1615,24 @@ extern "C" int32_t ldb_plan_stats(const ldb_plan* p, int64_t* executions, int64_
 }
 extern "C" const char* ldb_plan_json_last_error(void) { return g_plan_json_err.c_str(); }
 
-// the `fn` forms of a map step: extract_year / substr / upper / lower / length over "col", concat over "parts"
+// the `fn` forms of a map step: extract_year / substr / upper / lower / length / to_varchar over "col", to_int / to_decimal
+// (with "precision" and "scale") / to_date over "col" with an optional "on_error", concat over "parts"
 static void checkMapFn(const J& st, const std::string& out) {
    const std::string& fn = st.s("fn");
-   if (fn == "extract_year" || fn == "substr" || fn == "upper" || fn == "lower" || fn == "length") {
+   if (fn == "extract_year" || fn == "substr" || fn == "upper" || fn == "lower" || fn == "length" || fn == "to_varchar") {
       (void) st.s("col");
+      return;
+   }
+   if (fn == "to_int" || fn == "to_decimal" || fn == "to_date") { // precision and scale belong to to_decimal, and it needs both
+      const std::string where = "plan: map → '" + out + "': " + fn;
+      (void) st.s("col");
+      for (const char* f : {"precision", "scale"}) {
+         const J* v = st.get(f);
+         if (fn == "to_decimal" && (!v || v->kind != J::NUM)) throw std::runtime_error(where + " needs a number '" + f + "'");
+         if (fn != "to_decimal" && v) throw std::runtime_error(where + " takes no '" + f + "' (to_decimal only)");
+      }
+      if (const J* oe = st.get("on_error"))
+         if (oe->kind != J::STR || (oe->str != "fail" && oe->str != "null")) throw std::runtime_error(where + ": 'on_error' must be \"fail\" or \"null\"" + (oe->kind == J::STR ? ", not '" + oe->str + "'" : ""));
       return;
    }
    if (fn != "concat") {
@@ -1609,11 +1647,13 @@ static void checkMapFn(const J& st, const std::string& out) {
    for (auto& e : parts->arr) {
       const std::string where = "plan: map → '" + out + "': concat part " + std::to_string(k++);
       if (e.kind != J::OBJ) throw std::runtime_error(where + " must be an object");
-      const int given = (e.get("const") ? 1 : 0) + (e.get("col") ? 1 : 0) + (e.get("int") ? 1 : 0);
-      if (given != 1) throw std::runtime_error(where + " needs exactly one of 'const', 'col', 'int'");
-      if (e.get("const")) (void) e.s("const");
-      if (e.get("col")) (void) e.s("col");
-      if (e.get("int")) (void) e.s("int");
+      int given = 0;
+      for (const char* f : {"const", "col", "int", "dec", "date"})
+         if (e.get(f)) {
+            given++;
+            (void) e.s(f);
+         }
+      if (given != 1) throw std::runtime_error(where + " needs exactly one of 'const', 'col', 'int', 'dec', 'date'");
       if (const J* c = e.get("case")) {
          if (c->kind != J::STR) throw std::runtime_error(where + ": 'case' must be a string");
          (void) strcaseOf(c->str);

@@ -103,7 +103,8 @@ _STRCASE = {None: capi.SC_NONE, "none": capi.SC_NONE, "upper": capi.SC_UPPER, "l
 def str_parts(parts):
     """parts of ldb_gpu_map_strcat: bytes / str = a constant; {"col": (side, col), "case": "upper" | "lower", "from": f,
     "for": l} = a utf8 column, optionally a character window of it and a case mapping; {"int": (side, col)} = an int32 /
-    int64 column as decimal text; a capi.StrPart is taken as it is.  → (ctypes array, n, keepalive)"""
+    int64 column as decimal text; {"dec": (side, col)} = a decimal128 column and {"date": (side, col)} = a date32 column as
+    text; a capi.StrPart is taken as it is.  → (ctypes array, n, keepalive)"""
     arr = (capi.StrPart * max(len(parts), 1))()
     keep = []
     for k, p in enumerate(parts):
@@ -118,6 +119,10 @@ def str_parts(parts):
             sp.kind, sp.str, sp.str_len = capi.SP_CONST, b, len(b)
         elif "int" in p:
             sp.kind, sp.col = capi.SP_INT, colref(*p["int"])
+        elif "dec" in p:
+            sp.kind, sp.col = capi.SP_DECIMAL, colref(*p["dec"])
+        elif "date" in p:
+            sp.kind, sp.col = capi.SP_DATE, colref(*p["date"])
         else:
             sp.kind, sp.col = capi.SP_COL, colref(*p["col"])
             c = p.get("case")
@@ -383,6 +388,15 @@ class Rel:
         t = C.c_void_p()
         check(self.ctx.lib.ldb_gpu_map_strlen(self.ctx.h, self.h, colref(*col), name.encode(), C.byref(t)))
         return Table(self.ctx, t)
+
+    def map_strparse(self, col, kind, precision=0, scale=0, name="parsed", count_bad=True):
+        """a utf8 column parsed as capi.PARSE_INT64 / PARSE_DECIMAL (precision, scale) / PARSE_DATE: one nullable column, NULL
+        where the string is NULL or bad → (table, number of bad rows); count_bad = False passes no counter (nothing is
+        read back) and gives None for the count"""
+        t = C.c_void_p()
+        bad = C.c_int64(-1)
+        check(self.ctx.lib.ldb_gpu_map_strparse(self.ctx.h, self.h, colref(*col), kind, precision, scale, name.encode(), C.byref(t), C.byref(bad) if count_bad else None))
+        return Table(self.ctx, t), (bad.value if count_bad else None)
 
     def scan_count(self, plist):
         arr, n, keep = preds_array(plist)

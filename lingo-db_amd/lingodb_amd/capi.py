@@ -40,8 +40,10 @@ FN_EXTRACT_YEAR = 0
 # ldb_strpart_kind / ldb_strcase (ldb_gpu_map_strcat)
 LDB_MAX_STRPARTS = 8
 STR_WHOLE = 2 ** 63 - 1
-SP_COL, SP_CONST, SP_INT = range(3)
+SP_COL, SP_CONST, SP_INT, SP_DECIMAL, SP_DATE = range(5)
 SC_NONE, SC_UPPER, SC_LOWER = range(3)
+# ldb_parse_kind (ldb_gpu_map_strparse)
+PARSE_INT64, PARSE_DECIMAL, PARSE_DATE = range(3)
 
 
 class ColType(C.Structure):
@@ -225,6 +227,7 @@ GPU_API = {
     "ldb_gpu_map_substr": (i32, [P, P, ColRef, i64, i64, C.c_char_p, PP]),
     "ldb_gpu_map_strcat": (i32, [P, P, C.POINTER(StrPart), i32, C.c_char_p, PP]),
     "ldb_gpu_map_strlen": (i32, [P, P, ColRef, C.c_char_p, PP]),
+    "ldb_gpu_map_strparse": (i32, [P, P, ColRef, i32, i32, i32, C.c_char_p, PP, C.POINTER(i64)]),
     "ldb_gpu_scan_count": (i32, [P, P, C.POINTER(FilterDesc), i32, C.POINTER(i64)]),
     "ldb_gpu_hash_keys": (i32, [P, P, C.POINTER(ColRef), i32, PP]),
     "ldb_gpu_map_column": (i32, [P, P, ColRef, i32, C.c_char_p, PP]),
