@@ -284,7 +284,9 @@ int32_t ldb_gpu_table_col_width(const ldb_table* t, int32_t col);
  * bytewise string order of StringRuntime.cpp:242-256 — so predicates with constants test 4-byte codes and GROUP BY / ORDER
  * BY keys hash and compare codes; results, joins and the exchange still see the strings.  ldb_gpu_table_register and the
  * generator call it for every utf8 column (option `dict_encode`, tables of at least `dict_min_rows` rows); an explicit
- * call encodes a column of a smaller table.  *n_distinct / the return of _dict_size: dictionary entries, -1 = not encoded. */
+ * call encodes a column of a smaller table.  *n_distinct / the return of _dict_size: dictionary entries, -1 = not encoded.
+ * A column whose distinct values cannot be ordered (one longer than the 256 bytes of a string sort key, see ldb_gpu_sort)
+ * stays unencoded: the call and the registration succeed, ldb_gpu_last_error holds a note. */
 int32_t ldb_gpu_table_dict_encode(ldb_ctx* ctx, ldb_table* t, int32_t col, int32_t* n_distinct);
 int32_t ldb_gpu_table_dict_size(const ldb_table* t, int32_t col);
 /* raw device pointers (for RCCL exchange / zero-copy wrap); offsets/validity may be NULL.  The table's content stamp (ldb_gpu_table_stamp)
@@ -717,7 +719,11 @@ typedef struct {
 } ldb_sort_spec;
 /* Replaces GrowingBuffer::sort / parallelSort (GrowingBuffer.cpp:54-78, Sorting.cpp:343-393)
  * with comparator semantics of db.sort_compare (LowerToStd.cpp:1046-1064).  Stable w.r.t. input
- * order among equal keys (the reference's std::sort leaves that order unspecified). */
+ * order among equal keys (the reference's std::sort leaves that order unspecified).
+ * Float keys compare as db.cmp does (ordered compare): -0.0 and +0.0 are EQUAL keys, so the next
+ * key, then input order, decides between them.  The order of NaN keys is unspecified (the
+ * comparator is not an order on NaN).  1..8 keys; a utf8 key longer than 256 bytes, a key that
+ * holds a NULL, or a ninth key gives LDB_ERR_UNSUPPORTED. */
 int32_t ldb_gpu_sort(ldb_ctx* ctx, ldb_rel* in, const ldb_sort_spec* specs, int32_t n_specs, ldb_rel** out);
 /* Replaces Heap (Heap.cpp:8-72): first k rows of the sorted order. */
 int32_t ldb_gpu_topk(ldb_ctx* ctx, ldb_rel* in, const ldb_sort_spec* specs, int32_t n_specs, int64_t k, ldb_rel** out);

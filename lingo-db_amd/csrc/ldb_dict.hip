@@ -87,8 +87,7 @@ int32_t distinct_of(ldb_ctx* ctx, const ldb_table* v, int64_t limit, ldb_table**
 }
 } // namespace
 
-int32_t ldb_table_dict_encode(ldb_ctx* ctx, ldb_table* t, int32_t col, int32_t max_distinct) {
-   if (!ctx || !t || col < 0 || (size_t) col >= t->cols.size()) LDB_FAIL(LDB_ERR_INVALID, "dict_encode: bad argument");
+static int32_t dict_encode_column(ldb_ctx* ctx, ldb_table* t, int32_t col, int32_t max_distinct) {
    ldb_column& c = t->cols[(size_t) col];
    if (c.type.type != LDB_T_UTF8 || c.dict_codes || t->n_rows == 0) return LDB_OK;
    if (max_distinct > LDB_DICT_MAX) max_distinct = LDB_DICT_MAX;
@@ -134,6 +133,19 @@ int32_t ldb_table_dict_encode(ldb_ctx* ctx, ldb_table* t, int32_t col, int32_t m
    c.dict = dict.release();
    c.dict_size = (int32_t) nd;
    c.dict_pred_cache = new std::unordered_map<std::string, std::string>();
+   return LDB_OK;
+}
+
+// A dictionary is an optimisation: a column the operators above refuse to order or group (a string longer than the sort's 256-byte key limit)
+// stays a plain utf8 column and its table registers as usual.  Nothing of a half-built dictionary is attached (the column's fields are set
+// last, everything before them is scoped).  Like the library's other declined fast paths, the refusal stays readable as a note in
+// ldb_gpu_last_error; the status is LDB_OK.  Every other error is the caller's.
+int32_t ldb_table_dict_encode(ldb_ctx* ctx, ldb_table* t, int32_t col, int32_t max_distinct) {
+   if (!ctx || !t || col < 0 || (size_t) col >= t->cols.size()) LDB_FAIL(LDB_ERR_INVALID, "dict_encode: bad argument");
+   const int32_t st = dict_encode_column(ctx, t, col, max_distinct);
+   if (st != LDB_ERR_UNSUPPORTED) return st;
+   const std::string why = ldb_gpu_last_error();
+   ldb_set_error("dict_encode: column %d of '%s' stays unencoded (%s)", col, t->name.c_str(), why.c_str());
    return LDB_OK;
 }
 

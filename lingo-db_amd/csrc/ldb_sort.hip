@@ -96,6 +96,7 @@ __global__ void k_sort_keys(const DSort* __restrict__ d, uint64_t* __restrict__ 
             for (int k = 0; k < 4; k++) d_put_byte(rec, b + sp.str_pad + k, (uint8_t) ((len >> (24 - 8 * k)) ^ inv));
          } else if (sp.col.type == LDB_T_FLOAT64 || sp.col.type == LDB_T_FLOAT32) {
             uint64_t bits = (uint64_t) __double_as_longlong(d_load_f64(sp.col, row));
+            if ((bits << 1) == 0) bits = 0; // -0.0 = +0.0 under db.cmp (ordered float compare): one key, so the next sort key / input order decides
             bits = (bits >> 63) ? ~bits : (bits | 0x8000000000000000ull);
             for (int k = 0; k < 8; k++) d_put_byte(rec, b + k, (uint8_t) ((bits >> (56 - 8 * k)) ^ inv));
          } else if (sp.nbytes == 16) {
