@@ -678,7 +678,18 @@ int64_t ldb_gpu_hashtable_bytes(const ldb_hashtable* ht);
  * 2254-2313).  Output relation: INNER / LEFT_OUTER / SINGLE → sides = probe sides then build sides,
  * one row per match (LEFT_OUTER/SINGLE: unmatched probe rows carry LDB_NULL_ROW on build sides);
  * SEMI / ANTI → probe sides only, ascending; MARK → probe sides, all rows, plus *mark_out =
- * 1-column BOOL8 table.  NULL keys never match. */
+ * 1-column BOOL8 table.  NULL keys never match.
+ * Row order: SEMI / ANTI / MARK, SEMI_BUILD / ANTI_BUILD and the unmatched tail of RIGHT_OUTER / FULL_OUTER are ascending.  LEFT_OUTER and
+ * SINGLE over a build side whose promise of unique keys holds, and SINGLE over any build side, give exactly one row per probe row in probe
+ * order — unless the radix-clustered probe runs (option join_radix = 1, or its automatic choice for large unclustered probe sides), which
+ * gives the same rows cluster after cluster.  Every other pair-shaped result is a set of rows: no order is promised.
+ * SINGLE over build keys that repeat: the reference's single join takes whichever matching entry its chain walk meets (and may raise on a
+ * second one); here every probe row gets ONE of its partners (key equality and all residual conjuncts), which one is unspecified, and
+ * LDB_NULL_ROW exactly when it has none.
+ * Float keys follow db.hash plus db.cmp of the reference's hash join (HashLowering bit-casts the value, LowerToStd.cpp:1073-1132; the lookup
+ * compares the hash before the ordered compare, SubOpToControlFlow.cpp:2254-2313): two float keys match when their BIT PATTERNS are equal
+ * and they are no NaN.  +0.0 and -0.0 are therefore two join keys (they are ONE sort key, see ldb_gpu_sort below) and a NaN matches
+ * nothing, not even itself.  A float32 key column joins float32 only: the two widths hash differently. */
 int32_t ldb_gpu_join_probe(ldb_ctx* ctx, ldb_hashtable* ht, ldb_rel* probe, const ldb_colref* keys, int32_t n_keys,
                            int32_t kind, ldb_rel** out, ldb_table** mark_out);
 /* The same with residual conjuncts of the join predicate: a key match counts only when every

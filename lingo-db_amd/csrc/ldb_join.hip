@@ -284,12 +284,13 @@ __global__ void k_concat_rowids(const uint32_t* __restrict__ first, uint64_t na,
       out[i] = i < na ? (first ? first[i] : (uint32_t) i) : (pad_nulls ? LDB_NULL_ROW : (second ? second[i - na] : (uint32_t) (i - na)));
 }
 
-// debug_check option: largest row id of a selection vector (LDB_NULL_ROW ignored)
+// debug_check option: largest row id of a selection vector PLUS ONE — the rows its table must have; 0 when every entry is LDB_NULL_ROW (the
+// padded side of an outer join over an empty build side holds nothing else, and 0 rows are enough for it)
 __global__ void k_max_rowid(const uint32_t* __restrict__ ids, uint64_t n, unsigned int* __restrict__ out) {
    unsigned int mx = 0;
    for (uint64_t i = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x; i < n; i += (uint64_t) gridDim.x * blockDim.x) {
       const uint32_t v = ids[i];
-      if (v != LDB_NULL_ROW && v > mx) mx = v;
+      if (v != LDB_NULL_ROW && v + 1u > mx) mx = v + 1u;
    }
    if (mx) atomicMax(out, mx);
 }
@@ -301,8 +302,8 @@ static int32_t debug_check_ids(ldb_ctx* ctx, const char* what, const uint32_t* i
    uint64_t mx = 0;
    LDB_TRY(ldb_read_u64(ctx, d, &mx));
    mx &= 0xFFFFFFFFull;
-   if ((int64_t) mx >= limit)
-      LDB_FAIL(LDB_ERR_INVALID, "debug_check: %s row id %llu >= %lld (kind %d key32 %d ordered %d key_bits %d chained %d unique %d n_ppreds %d n_rows %llu cap %llu)", what, (unsigned long long) mx,
+   if ((int64_t) mx > limit)
+      LDB_FAIL(LDB_ERR_INVALID, "debug_check: %s row id %llu >= %lld (kind %d key32 %d ordered %d key_bits %d chained %d unique %d n_ppreds %d n_rows %llu cap %llu)", what, (unsigned long long) mx - 1,
                (long long) limit, h->kind, h->key32, h->ordered_slots, h->has_key_bits, h->chained, h->build_unique, h->n_ppreds, (unsigned long long) h->n_rows, (unsigned long long) h->cap);
    return LDB_OK;
 }
