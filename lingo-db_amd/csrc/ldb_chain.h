@@ -1,4 +1,4 @@
-// ldb_chain.h — building blocks of the single-launch (chained, decoupled look-back) scans: ldb_core.hip's exclusive scans and
+// ldb_chain.h — building blocks of the single-launch (chained, decoupled look-back) scans: ldb_prims.hip's exclusive scans and
 // bitmap compaction, the rank-table prefix pass of ldb_join.hip, the occupancy scan of ldb_gbhost.hip.
 // A tile of CHAIN_TILE elements per workgroup of 256; tile numbers come from a ticket counter (a tile only ever waits for
 // tiles whose workgroups are already running); per-tile status words {epoch, state, value} are never cleared: every call owns

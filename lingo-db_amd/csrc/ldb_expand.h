@@ -1,5 +1,5 @@
 // ldb_expand.h — a tile of selection-bitmap words → the ascending list of its set row numbers, for a workgroup of 256: the
-// expansion shared by k_scan_expand (ldb_scan.hip) and k_bitmap_compact (ldb_core.hip).
+// expansion shared by k_scan_expand (ldb_scan.hip) and k_bitmap_compact (ldb_prims.hip).
 // A tile is 256 * ITEMS words; word w of the tile belongs to thread w % 256 (round w / 256).  The row ids go through an LDS
 // staging buffer, EXPAND_CHUNK at a time: every thread drops the set bits of its own words at their output positions inside
 // the chunk (LDS stores only), then the workgroup streams the chunk out — consecutive lanes write consecutive addresses, and

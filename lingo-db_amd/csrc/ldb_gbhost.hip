@@ -780,7 +780,7 @@ struct GbState {
          // ordered slots give up on long probe runs, which depends on the insertion order: should a REPLAYED execution
          // (ldb_readback) meet that where the recorded one did not, its group count is too high until the trace ends and the
          // execution is repeated — the representative rows beyond the real count must then still be valid row numbers
-         if (h->ordered_slots && ctx->trace_mode == 2) LDB_HIP(hipMemsetAsync(rep_rows, 0, 4 * (size_t) max_groups, ctx->stream));
+         if (h->ordered_slots && ldb_replaying(ctx)) LDB_HIP(hipMemsetAsync(rep_rows, 0, 4 * (size_t) max_groups, ctx->stream));
       }
       for (int32_t a = 0; a < n_aggs; a++) {
          LDB_TRY(outs.alloc(&out_vals[(size_t) a], (size_t) h->outs[a].out_width * (size_t) max_groups));

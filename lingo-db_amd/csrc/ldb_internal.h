@@ -79,6 +79,8 @@ int32_t ldb_column_range(ldb_ctx* ctx, const struct ldb_table* t, int32_t col, i
 // is the (integer-like, NOT NULL) column stored in non-decreasing order?  Cached like the range.
 int32_t ldb_column_sorted(ldb_ctx* ctx, const struct ldb_table* t, int32_t col, bool* sorted);
 
+struct ldb_ctx;
+// ---------------------------------------------------------------- per-kernel profiling (ldb_core.hip)
 struct ldb_prof_pending {
    const char* name;
    hipEvent_t start, stop;
@@ -89,9 +91,66 @@ struct ldb_prof_total {
    double ms = 0;
    double max_ms = 0; // the longest single launch (an operator may launch the same kernel on inputs of very different size)
 };
-#define LDB_RING_BYTES ((size_t) 1 << 20)
+struct ldb_prof_state {
+   bool on = false;
+   std::vector<ldb_prof_pending> pending;
+   std::vector<ldb_prof_total> totals;
+   std::vector<hipEvent_t> free_events;
+};
+// kernel timing scope: LdbProf p(ctx, "k_name"); <launch>; (destructor records the stop event)
+struct LdbProf {
+   ldb_ctx* ctx;
+   size_t idx = 0;
+   bool active = false;
+   LdbProf(ldb_ctx* c, const char* name);
+   ~LdbProf();
+};
 
-// ---------------------------------------------------------------- read-backs and their trace (prepared plans)
+// ---------------------------------------------------------------- device memory (ldb_mem.hip)
+#define LDB_RING_BYTES ((size_t) 1 << 20)
+struct ldb_mem_state {
+   // Block cache in front of the stream-ordered pool (ldb_dev_alloc / ldb_dev_free): every operator
+   // call allocates ~10 temporaries, and a hipMallocAsync + hipFreeAsync pair costs ~15 µs of host
+   // time — more than many of the kernels between them.  All work of a context is ordered on
+   // ctx->stream, so a freed block may be handed to the next allocation without any wait.
+   uint8_t* h_ring = nullptr; // pinned staging ring of ldb_dev_upload
+   size_t ring_pos = 0;
+   bool cache_on = true;
+   size_t parked_bytes = 0, parked_cap = 0; // bytes parked in free lists / their limit
+   std::unordered_map<void*, size_t> live; // block → its size class (bytes)
+   std::unordered_map<size_t, std::vector<void*>> parked; // size class → free blocks (min-heaps by address: the lowest free block is handed out, so a
+                                                          // repeated plan sees the same addresses whatever order its blocks were freed in)
+   // descriptor cache of ldb_dev_upload: content hash → device copy (never written by a kernel: descriptors are const)
+   struct DescEntry {
+      void* dev;
+      std::vector<uint8_t> copy;
+   };
+   std::unordered_multimap<uint64_t, DescEntry> desc_cache;
+   std::unordered_map<void*, int> desc_blocks; // device copy → operators holding it (ldb_dev_upload … ldb_dev_free)
+   std::unordered_map<void*, int> shared; // block → EXTRA holders beyond the first (ldb_dev_share): ldb_dev_free gives one back, the last one frees
+   size_t desc_bytes = 0;
+   int64_t desc_hits = 0, desc_misses = 0, desc_underflows = 0; // (underflow: a reference given back that nobody held — a caller's bug, counted and reported)
+};
+// device allocation helpers (stream-ordered pool)
+int32_t ldb_dev_alloc(ldb_ctx* ctx, void** out, size_t bytes);
+void ldb_dev_free(ldb_ctx* ctx, void* p);
+// one more holder of a read-only block (the row-id vector of a relation side carried over unchanged into the next relation): every holder calls
+// ldb_dev_free, the last call frees
+void ldb_dev_share(ldb_ctx* ctx, void* p);
+// upload a host descriptor struct into device memory (stream-ordered)
+// (read-only descriptors are cached by content, see ldb_mem.hip; cacheable = false for memory a kernel will write)
+int32_t ldb_dev_upload(ldb_ctx* ctx, const void* host, size_t bytes, void** dev_out, bool cacheable = true);
+// a few bytes host → device through the pinned staging ring: a plain asynchronous DMA (hipMemcpyAsync from pageable memory is staged by the
+// runtime and WAITS for the stream — inside a replayed plan that is the whole queue)
+int32_t ldb_h2d_small(ldb_ctx* ctx, void* dev, const void* host, size_t bytes);
+// with the context: ldb_mem_init sets the block cache up (pool threshold, LDB_ALLOC_CACHE, the limit of parked bytes) and allocates the staging
+// ring.  Teardown is two steps around the caller's stream synchronisation: ldb_mem_release_blocks queues the stream-ordered frees of every
+// cached descriptor and parked block; ldb_mem_teardown frees the staging ring, which copies still queued on the stream may read
+int32_t ldb_mem_init(ldb_ctx* ctx);
+void ldb_mem_release_blocks(ldb_ctx* ctx);
+void ldb_mem_teardown(ldb_ctx* ctx);
+
+// ---------------------------------------------------------------- read-backs and their trace (prepared plans; ldb_trace.hip)
 // Every device → host read of a count / flag / control block goes through ldb_readback.  Outside a trace it is an
 // asynchronous copy followed by a stream synchronisation (the host needs the value to size the next allocation).  Inside a
 // trace (ldb_gpu_trace_begin … _end, what a prepared plan brackets each execution with) the values are RECORDED in call
@@ -137,47 +196,21 @@ struct ldb_ctx;
 #define LDB_RB_ORDER_DEPENDENT 2
 int32_t ldb_readback(ldb_ctx* ctx, void* host, const void* dev, size_t bytes, uint32_t site, int flags = 0);
 #define LDB_READBACK(ctx, host, dev, bytes) ldb_readback((ctx), (host), (dev), (bytes), LDB_SITE)
-
-struct ldb_ctx {
-   bool prof_on = false;
-   std::vector<ldb_prof_pending> prof_pending;
-   std::vector<ldb_prof_total> prof_totals;
-   std::vector<hipEvent_t> prof_free;
-   int device = 0;
-   hipStream_t stream = nullptr;
-   bool own_stream = false;
-   int cus = 256;
-   std::vector<hipEvent_t> timers; // pairs (start, stop)
-   // small pinned staging area for counts read back from the device
-   int64_t* h_scratch = nullptr; // pinned, 64 words
-   int64_t* d_scratch = nullptr; // device, 64 words
-   // Block cache in front of the stream-ordered pool (ldb_dev_alloc / ldb_dev_free): every operator
-   // call allocates ~10 temporaries, and a hipMallocAsync + hipFreeAsync pair costs ~15 µs of host
-   // time — more than many of the kernels between them.  All work of a context is ordered on
-   // ctx->stream, so a freed block may be handed to the next allocation without any wait.
-   uint8_t* h_ring = nullptr; // pinned staging ring of ldb_dev_upload
-   size_t ring_pos = 0;
-   bool cache_on = true;
-   size_t cache_bytes = 0, cache_cap = 0; // bytes parked in free lists / their limit
-   std::unordered_map<void*, size_t> live; // block → its size class (bytes)
-   std::unordered_map<size_t, std::vector<void*>> parked; // size class → free blocks (min-heaps by address: the lowest free block is handed out, so a
-                                                          // repeated plan sees the same addresses whatever order its blocks were freed in)
-   // descriptor cache of ldb_dev_upload: content hash → device copy (never written by a kernel: descriptors are const)
-   struct DescEntry {
-      void* dev;
-      std::vector<uint8_t> copy;
-   };
-   std::unordered_multimap<uint64_t, DescEntry> desc_cache;
-   std::unordered_map<void*, int> desc_blocks; // device copy → operators holding it (ldb_dev_upload … ldb_dev_free)
-   std::unordered_map<void*, int> shared; // block → EXTRA holders beyond the first (ldb_dev_share): ldb_dev_free gives one back, the last one frees
-   size_t desc_bytes = 0;
-   int64_t desc_hits = 0, desc_misses = 0, desc_underflows = 0; // (underflow: a reference given back that nobody held — a caller's bug, counted and reported)
+// read of one 64-bit device word (ldb_readback)
+int32_t ldb_read_u64_at(ldb_ctx* ctx, const void* d_word, uint64_t* out, uint32_t site, int flags = 0);
+#define ldb_read_u64(ctx, d_word, out) ldb_read_u64_at((ctx), (d_word), (out), LDB_SITE)
+#define LDB_ARENA_WORDS 16384
+// n_words zeroed 64-bit device words (64-byte aligned) that stay this caller's until the arena wraps: written by its kernels,
+// read back with ldb_readback; never cleared, never reused for a second purpose by the caller after the read-back
+int32_t ldb_counters(ldb_ctx* ctx, int n_words, uint64_t** out);
+enum class ldb_rb_mode { off, record, replay };
+struct ldb_rb_state {
    // read-back trace (see ldb_readback)
    ldb_trace* trace = nullptr;
-   int trace_mode = 0; // 0 none, 1 record, 2 replay
-   size_t trace_pos = 0;
-   bool trace_poisoned = false; // a replayed value was wrong: everything computed since is void
-   bool trace_collective = false; // the traced plan exchanges rows with other ranks: a mis-speculating rank runs on (see ldb_readback)
+   ldb_rb_mode mode = ldb_rb_mode::off;
+   size_t pos = 0;
+   bool poisoned = false; // a replayed value was wrong: everything computed since is void
+   bool collective = false; // the traced plan exchanges rows with other ranks: a mis-speculating rank runs on (see ldb_readback)
    uint8_t* h_log = nullptr; // pinned, LDB_LOG_BYTES
    // counter arena (ldb_counters): zeroed 64-bit device words handed out front to back — an operator's counters / flags / totals
    // are words nobody else touches until the arena wraps, so (a) no operator clears its counters itself (one clear per plan
@@ -191,14 +224,51 @@ struct ldb_ctx {
       uint32_t off, bytes;
    };
    std::vector<LogCopy> log_pending; // deferred copies of a replaying trace: arena words → pinned log
-   // single-pass scans (ldb_exclusive_scan_*): tile status words + the ticket counter, never cleared — every scan call owns a
-   // fresh epoch / ticket range (ldb_core.hip)
-   uint64_t* scan_status = nullptr;
-   size_t scan_status_tiles = 0;
-   unsigned long long* scan_ticket = nullptr; // device
-   uint64_t scan_ticket_base = 0; // tickets handed out so far (host mirror)
-   uint32_t scan_epoch = 0;
 };
+// context teardown: the pinned log and the arena (the caller has synchronised the stream)
+void ldb_trace_teardown(ldb_ctx* ctx);
+
+// ---------------------------------------------------------------- scan chain (ldb_chain.h, ldb_prims.hip)
+// single-pass scans (ldb_exclusive_scan_*): tile status words + the ticket counter, never cleared — every scan call owns a
+// fresh epoch / ticket range (ldb_chain_begin)
+struct ldb_chain_state {
+   uint64_t* status = nullptr;
+   size_t status_tiles = 0;
+   unsigned long long* ticket = nullptr; // device
+   uint64_t ticket_base = 0; // tickets handed out so far (host mirror)
+   uint32_t epoch = 0;
+};
+// context teardown: the status words and the ticket counter (the caller has synchronised the stream)
+void ldb_chain_teardown(ldb_ctx* ctx);
+
+// ---------------------------------------------------------------- the context
+// Who owns which 64-bit words of ldb_ctx::d_scratch.  Every user writes its words, launches and queues its read (ldb_readback) on
+// ctx->stream before it returns, so users of the same words never overlap; a new user takes words nobody has.
+enum ldb_scratch_word {
+   LDB_SCRATCH_JOIN_KEY_RANGE = 32, // 32–33: min / max of the join build's keys (ldb_join.hip)
+   LDB_SCRATCH_COLUMN_RANGE = 40, // 40–41: ldb_column_range's min / max (ldb_colstats.hip) …
+   LDB_SCRATCH_JOIN_MAX_ROWID = 40, // … 40: debug_check_ids' largest row id (ldb_join.hip) …
+   LDB_SCRATCH_JOIN_LOCALITY = 40, // … 40: the clustered-probe sample's near / valid counts (ldb_join.hip)
+   LDB_SCRATCH_COLUMN_SORTED = 44, // 44: ldb_column_sorted's "out of order" flag (ldb_colstats.hip)
+};
+struct ldb_ctx {
+   int device = 0;
+   hipStream_t stream = nullptr;
+   bool own_stream = false;
+   int cus = 256;
+   std::vector<hipEvent_t> timers; // pairs (start, stop)
+   // small pinned staging area for counts read back from the device
+   int64_t* h_scratch = nullptr; // pinned, 64 words
+   int64_t* d_scratch = nullptr; // device, 64 words (ldb_scratch_word)
+   ldb_mem_state mem;
+   ldb_rb_state rb;
+   ldb_chain_state chain;
+   ldb_prof_state prof;
+};
+// Is this execution replaying a recorded trace?  Then a count the caller reads back may be the RECORDED value, which can exceed what the
+// kernels of this execution really produce (the difference is only found at the trace's end, and the execution repeated): whatever the caller
+// sizes from such a count it must initialise itself — no uninitialised row id may be left behind the real tail for a consumer to follow.
+static inline bool ldb_replaying(const ldb_ctx* ctx) { return ctx->rb.mode == ldb_rb_mode::replay; }
 
 uint64_t ldb_next_serial();
 struct ldb_table {
@@ -241,15 +311,6 @@ struct ldb_rel {
 // materialise a lazy relation in place (no-op otherwise)
 int32_t ldb_rel_force(ldb_ctx* ctx, ldb_rel* r);
 
-// kernel timing scope: LdbProf p(ctx, "k_name"); <launch>; (destructor records the stop event)
-struct LdbProf {
-   ldb_ctx* ctx;
-   size_t idx = 0;
-   bool active = false;
-   LdbProf(ldb_ctx* c, const char* name);
-   ~LdbProf();
-};
-
 // diagnostics (env LDB_HOST_TRACE=<ms>): host calls that took longer than <ms> milliseconds are reported on stderr with their site — how a
 // blocking call inside a replayed plan is found without a profiler (LDB_HOST_TRACE=0.2 python bench.py …)
 double ldb_host_trace_threshold();
@@ -267,18 +328,6 @@ struct LdbSlow {
       if (ms >= thr) fprintf(stderr, "[ldb host] %s(%zu): %.3f ms\n", what, arg, ms);
    }
 };
-// device allocation helpers (stream-ordered pool)
-int32_t ldb_dev_alloc(ldb_ctx* ctx, void** out, size_t bytes);
-void ldb_dev_free(ldb_ctx* ctx, void* p);
-// one more holder of a read-only block (the row-id vector of a relation side carried over unchanged into the next relation): every holder calls
-// ldb_dev_free, the last call frees
-void ldb_dev_share(ldb_ctx* ctx, void* p);
-// upload a host descriptor struct into device memory (stream-ordered)
-// (read-only descriptors are cached by content, see ldb_core.hip; cacheable = false for memory a kernel will write)
-int32_t ldb_dev_upload(ldb_ctx* ctx, const void* host, size_t bytes, void** dev_out, bool cacheable = true);
-// a few bytes host → device through the pinned staging ring: a plain asynchronous DMA (hipMemcpyAsync from pageable memory is staged by the
-// runtime and WAITS for the stream — inside a replayed plan that is the whole queue)
-int32_t ldb_h2d_small(ldb_ctx* ctx, void* dev, const void* host, size_t bytes);
 
 // device temporaries of one call: whatever is still listed when the scope ends is freed (error returns included)
 struct LdbBufs {
@@ -441,10 +490,10 @@ static inline uint64_t next_pow2_u64(uint64_t v) {
    while (p < v) p <<= 1;
    return p;
 }
-// out[i] = i (ldb_core.hip); launched from several translation units — host launches only, never called from device code (no -fgpu-rdc)
+// out[i] = i (ldb_rel.hip); launched from several translation units — host launches only, never called from device code (no -fgpu-rdc)
 __global__ void k_iota_u32(uint32_t* out, uint64_t n);
 // the rows of `in` that sel[0, n_sel) names, as a relation of its own — takes `sel` over, on error returns too (ldb_scan.hip); their columns
-// `refs` materialised into outs[0, n_cols) (ldb_core.hip)
+// `refs` materialised into outs[0, n_cols) (ldb_rel.hip)
 int32_t ldb_rel_select(ldb_ctx* ctx, ldb_rel* in, uint32_t* sel, int64_t n_sel, ldb_rel** out);
 int32_t ldb_gather_columns(ldb_ctx* ctx, const ldb_rel* r, const ldb_colref* refs, int32_t n_cols, ldb_column* outs);
 // MIN / MAX over utf8 columns — a selection row per aggregate: the extreme string's row, LDB_NULL_ROW when every argument is NULL (ldb_strminmax.hip)
@@ -475,15 +524,8 @@ int32_t ldb_compose_rowids(ldb_ctx* ctx, const uint32_t* sel0, const uint32_t* s
 // caller afterwards, may be NULL): begin of partition q at [q * *chunks_out].  prof_* = string literals.
 int32_t ldb_wc_partition(ldb_ctx* ctx, const uint32_t* keys_in, const uint32_t* pay_in, uint64_t n, uint32_t bias, uint32_t range, uint32_t shift, uint32_t nparts, uint32_t* keys_out,
                          uint32_t* pay_out, uint32_t** part_offs_out, uint32_t* chunks_out, const char* prof_hist, const char* prof_scatter);
-#define LDB_ARENA_WORDS 16384
-// n_words zeroed 64-bit device words (64-byte aligned) that stay this caller's until the arena wraps: written by its kernels,
-// read back with ldb_readback; never cleared, never reused for a second purpose by the caller after the read-back
-int32_t ldb_counters(ldb_ctx* ctx, int n_words, uint64_t** out);
 // selection bitmap (n_words x 64 rows) → ascending row numbers in out[0, total), total ≤ cap; entries [total, cap) are set
 // to 0; with `match`, second[j] = match[out[j]]; *d_total (device, may be NULL) receives the count.  One launch.
 int32_t ldb_bitmap_compact(ldb_ctx* ctx, const uint64_t* bitmap, int64_t n_words, uint32_t* out, uint64_t cap, const uint32_t* match, uint32_t* second, uint64_t* d_total);
-// read of one 64-bit device word (ldb_readback)
-int32_t ldb_read_u64_at(ldb_ctx* ctx, const void* d_word, uint64_t* out, uint32_t site, int flags = 0);
-#define ldb_read_u64(ctx, d_word, out) ldb_read_u64_at((ctx), (d_word), (out), LDB_SITE)
 // new relation helpers
 ldb_rel* ldb_rel_new(ldb_ctx* ctx);

@@ -296,7 +296,7 @@ __global__ void k_max_rowid(const uint32_t* __restrict__ ids, uint64_t n, unsign
 }
 static int32_t debug_check_ids(ldb_ctx* ctx, const char* what, const uint32_t* ids, uint64_t n, int64_t limit, const DJoin* h) {
    if (!ids || !n) return LDB_OK;
-   unsigned int* d = (unsigned int*) (ctx->d_scratch + 40);
+   unsigned int* d = (unsigned int*) (ctx->d_scratch + LDB_SCRATCH_JOIN_MAX_ROWID);
    LDB_HIP(hipMemsetAsync(d, 0, 8, ctx->stream));
    hipLaunchKernelGGL(k_max_rowid, dim3(ldb_grid_for(ctx, (int64_t) n, 256, 4)), dim3(256), 0, ctx->stream, ids, n, d);
    uint64_t mx = 0;
@@ -518,7 +518,7 @@ static int32_t radix_prepare(ldb_ctx* ctx, ldb_hashtable* ht, ldb_rel* probe, co
    d.slot32 = (uint32_t) ht->slot32;
    d.direct = (uint32_t) ht->direct;
    if (mode < 0) { // already clustered on the key?  then the table is walked sequentially as it is
-      unsigned int* dl = (unsigned int*) (ctx->d_scratch + 40);
+      unsigned int* dl = (unsigned int*) (ctx->d_scratch + LDB_SCRATCH_JOIN_LOCALITY);
       LDB_HIP(hipMemsetAsync(dl, 0, 8, ctx->stream));
       const uint64_t samples = 1 << 16, stride = std::max<uint64_t>(1, (uint64_t) n / samples);
       hipLaunchKernelGGL(k_radix_locality, dim3((unsigned) (samples / 256)), dim3(256), 0, ctx->stream, d, stride, dl);
@@ -699,7 +699,7 @@ struct JoinBuild {
          got[0] = clo;
          got[1] = chi;
       } else {
-         long long* range = (long long*) (ctx->d_scratch + 32);
+         long long* range = (long long*) (ctx->d_scratch + LDB_SCRATCH_JOIN_KEY_RANGE);
          const long long init[2] = {INT64_MAX, INT64_MIN};
          LDB_TRY(ldb_h2d_small(ctx, range, init, 16));
          LdbDesc<DJoin> dr_desc(ctx);
@@ -1233,7 +1233,7 @@ static int32_t probe_unique(ldb_ctx* ctx, ldb_hashtable* ht, ldb_rel* probe, Pro
       // relation's rows in the probe relation's order, so its sides carry over as they are — shared, not copied — and match[] IS the
       // build side's selection.  No bitmap compaction, no composition of the probe sides (round 6; the reference never materialises
       // between the operators of a pipeline either, SubOpToControlFlow.cpp:1123-1202)
-      if (ctx->trace_mode == 2 && n_words) // a replayed count: should a row be partner-less after all, its match[] word must not be garbage
+      if (ldb_replaying(ctx) && n_words) // a replayed count: should a row be partner-less after all, its match[] word must not be garbage
          hipLaunchKernelGGL(k_unmatched_to_zero, dim3(ldb_grid_for(ctx, (int64_t) n_words, 256, 8)), dim3(256), 0, ctx->stream, (const uint64_t*) bitmap, match, (uint64_t) n);
       bufs.free(bitmap);
       LdbRelHold r(ctx, ldb_rel_new(ctx));
@@ -1280,7 +1280,7 @@ static int32_t probe_pairs(ldb_ctx* ctx, ldb_hashtable* ht, ldb_rel* probe, Prob
    LDB_TRY(bufs.alloc(&op, 4 * (size_t) (produced ? produced : 1)));
    LDB_TRY(bufs.alloc(&ob, 4 * (size_t) (produced ? produced : 1)));
    if (produced) {
-      if (ctx->trace_mode == 2) { // a replayed `produced` may exceed what the kernel really emits: no uninitialised row id behind the real tail
+      if (ldb_replaying(ctx)) { // a replayed `produced` may exceed what the kernel really emits: no uninitialised row id behind the real tail
          LDB_HIP(hipMemsetAsync(op, 0, 4 * (size_t) produced, ctx->stream));
          LDB_HIP(hipMemsetAsync(ob, 0, 4 * (size_t) produced, ctx->stream));
       }
