@@ -72,6 +72,41 @@ def test_structure_check_names_what_is_wrong():
     assert st == 0, err
 
 
+def test_structure_check_knows_every_step_the_shipped_plans_use():
+    """every "op" that occurs in a shipped plan file (plans/tpch, plans/tpch/dist, plans/job, plans/subop; loop bodies included) is accepted in a
+    minimal well-formed step — the check reads the interpreter's own step table — and the same op spelled wrongly is refused"""
+    import glob
+
+    def ops(steps):
+        for s in steps:
+            yield s["op"]
+            yield from ops(s.get("body", []))
+
+    used = set()
+    for sub in ("tpch", os.path.join("tpch", "dist"), "job", "subop"):
+        files = glob.glob(os.path.join(ROOT, "lingo-db_amd", "plans", sub, "*.json"))
+        assert files, sub
+        for path in files:
+            with open(path) as f:
+                used |= set(ops(json.load(f)["steps"]))
+    minimal = {"scan": {"table": "t"}, "filter": {"in": "t", "preds": []}, "filter_dnf": {"in": "t", "clauses": []}, "join_build": {"in": "t", "keys": []},
+               "join_probe": {"ht": "h", "in": "t", "keys": []}, "groupby": {"in": "t", "aggs": []}, "map": {"in": "t", "as": "c", "expr": 1}, "sort": {"in": "t", "by": []},
+               "topk": {"in": "t", "by": [], "k": 1}, "materialize": {"in": "t", "cols": []}, "join_nl": {"in": "t", "build": "t"}, "allgather": {"in": "t"},
+               "shuffle": {"in": "t", "keys": [], "cols": []}, "nested_map": {"in": "t", "scan": "t"}, "set_op": {"left": "t", "right": "t", "left_cols": [], "right_cols": [], "kind": "union"},
+               "window": {"in": "t", "fns": []},
+               "loop": {"vars": [{"name": "v", "init": "t"}], "body": [{"op": "materialize", "in": "v", "cols": [], "out": "n"}], "continue": {"from": "n", "col": "c"},
+                        "next": [{"var": "v", "from": "n"}], "results": [{"name": "x", "var": "v"}]}}
+    assert len(used) >= 10 and used <= set(minimal), sorted(used - set(minimal))
+    build = {"op": "join_build", "in": "t", "keys": [], "out": "h"}
+    for op in sorted(used):
+        good = {"steps": [build, dict(minimal[op], op=op, out="x")], "result": "x"}
+        st, err = _check(json.dumps(good), ["t"])
+        assert st == 0, (op, err)
+        bad = {"steps": [build, dict(minimal[op], op=op + "s", out="x")], "result": "x"}
+        st, err = _check(json.dumps(bad), ["t"])
+        assert st != 0 and "plan: unknown step '%ss'" % op in err, (op, err)
+
+
 def test_database_generates_every_column_a_plan_names():
     """bench.py's Database generates only the columns the selected queries touch: every TPC-H column a plan
     file names must be among them, per query (checked with a recording stand-in for the device context)"""
