@@ -422,6 +422,34 @@ int32_t ldb_gpu_hash_keys(ldb_ctx* ctx, ldb_rel* in, const ldb_colref* keys, int
  * attached to the relation with ldb_gpu_rel_zip. */
 typedef enum { LDB_FN_EXTRACT_YEAR = 0 /* date32 → int64 civil year */ } ldb_scalar_fn;
 int32_t ldb_gpu_map_column(ldb_ctx* ctx, ldb_rel* in, ldb_colref col, int32_t fn, const char* name, ldb_table** out);
+/* Date and time functions as computed columns: extract / date_trunc / date ± interval month — the runtime calls
+ * ExtractYear … ExtractSecondFromDate, DateTrunc, DateAdd and DateSubtract of the reference (src/runtime/DateRuntime.cpp
+ * :99-116, :117-164, :77-82 with DateHelper::addMonths :35-40; registered in RuntimeFunctions.cpp:316-330).  The reference
+ * holds dates and timestamps alike as int64 ns since the epoch and goes through floor<days> and the proleptic Gregorian
+ * calendar in UTC; here `col` is a DATE32 column (days, and the result of TRUNC / ADD_MONTHS stays days) or an INT64 column
+ * of ns since the epoch (a timestamp).
+ *   - LDB_DF_EXTRACT: `part` of the instant as INT64.  Floor semantics: -1 ns is 1969-12-31 23:59:59.  SECOND is the whole
+ *     second.  Over DATE32, hour / minute / second are 0.  Defined for every int64 instant and every int32 day.
+ *   - LDB_DF_TRUNC: the parts up to `part` kept, every finer one at its first value (dateTrunc → toEpochNs); the input's
+ *     type.  Over DATE32, day / hour / minute / second are the identity.  An int64 instant before 1678-01-01T00:00:00
+ *     truncates to a value outside int64 (signed overflow in the reference as well): the wrapped value is returned.
+ *   - LDB_DF_ADD_MONTHS: the instant `months` months later (earlier when negative; DateSubtract is -months); the input's
+ *     type.  `months_col` (INT32 / INT64), when not NULL, gives the months per row instead of the constant.  Year and month
+ *     are normalised by floor division by 12, day of the month and time of day are kept, and a day past the end of the
+ *     target month is NOT clamped: it runs over into the next month, because sys_days{ymd} of a day that does not exist is
+ *     plain day arithmetic (2023-01-31 + 1 = 2023-03-03, 2024-01-31 + 1 = 2024-03-02, 2023-03-31 - 1 = 2023-03-03).  This
+ *     differs from PostgreSQL, which clamps to the last day of the month.  The result column is always nullable: a row is
+ *     NULL when its input or its month value is NULL, and when the result leaves the type's range — a day outside
+ *     -719162 … 2932896 (0001-01-01 … 9999-12-31, the range of the DATE string part) for DATE32, an instant outside
+ *     int64 ns for a timestamp; |months| > 240000 is out of range by construction.
+ * `months` / `months_col` are ignored unless fn is ADD_MONTHS; `part` is ignored for ADD_MONTHS.  NULL in → NULL out, row
+ * ids and outer-join padding included.  LDB_ERR_INVALID, with no work done, for a NULL ctx / in / out, an unknown fn or
+ * part, a `col` that is neither DATE32 nor INT64 and a `months_col` that is neither INT32 nor INT64.  No rows give an
+ * empty column of the result type.  date_diff needs no entry point: it is SUB / SDIV of ldb_gpu_map_expr (:83-98). */
+typedef enum { LDB_DF_EXTRACT = 0, LDB_DF_TRUNC = 1, LDB_DF_ADD_MONTHS = 2 } ldb_datefn;
+typedef enum { LDB_DP_YEAR = 0, LDB_DP_MONTH = 1, LDB_DP_DAY = 2, LDB_DP_HOUR = 3, LDB_DP_MINUTE = 4, LDB_DP_SECOND = 5 } ldb_datepart;
+int32_t ldb_gpu_map_datefn(ldb_ctx* ctx, ldb_rel* in, ldb_colref col, int32_t fn, int32_t part, int64_t months, const ldb_colref* months_col /* NULL: the constant */,
+                           const char* name, ldb_table** out);
 /* Arithmetic on aggregate results (a16): `literal * num / den` over two decimal or integer columns
  * as one decimal128(out_precision, out_scale) column,
  *    out = ((((num * mul) sdiv 10^mul_div_pow10) * 10^pow10) sdiv den   in wrapping 128-bit arithmetic,

@@ -214,7 +214,8 @@ extern "C" int32_t ldb_plan_stats(const ldb_plan* p, int64_t* executions, int64_
 extern "C" const char* ldb_plan_json_last_error(void) { return g_plan_json_err.c_str(); }
 
 // the `fn` forms of a map step: extract_year / substr / upper / lower / length / to_varchar over "col", to_int / to_decimal
-// (with "precision" and "scale") / to_date over "col" with an optional "on_error", concat over "parts"
+// (with "precision" and "scale") / to_date over "col" with an optional "on_error", concat over "parts", extract / date_trunc
+// over "col" with a "part", add_months over "col" with exactly one of "months" (a number) and "months_col"
 static void checkMapFn(const J& st, const std::string& out) {
    const std::string& fn = st.s("fn");
    if (fn == "extract_year" || fn == "substr" || fn == "upper" || fn == "lower" || fn == "length" || fn == "to_varchar") {
@@ -231,6 +232,22 @@ static void checkMapFn(const J& st, const std::string& out) {
       }
       if (const J* oe = st.get("on_error"))
          if (oe->kind != J::STR || (oe->str != "fail" && oe->str != "null")) throw std::runtime_error(where + ": 'on_error' must be \"fail\" or \"null\"" + (oe->kind == J::STR ? ", not '" + oe->str + "'" : ""));
+      return;
+   }
+   if (fn == "extract" || fn == "date_trunc" || fn == "add_months") {
+      const std::string where = "plan: map → '" + out + "': " + fn;
+      (void) st.s("col");
+      if (fn == "add_months") {
+         const J *m = st.get("months"), *mc = st.get("months_col");
+         if (m && mc) throw std::runtime_error(where + " takes 'months' or 'months_col', not both");
+         if (!m && !mc) throw std::runtime_error(where + " needs 'months' (a number) or 'months_col'");
+         if (m && m->kind != J::NUM) throw std::runtime_error(where + ": 'months' must be a number");
+         if (mc) (void) st.s("months_col");
+         return;
+      }
+      const J* part = st.get("part");
+      if (!part || part->kind != J::STR) throw std::runtime_error(where + " needs a 'part' (year, month, day, hour, minute, second)");
+      if (datepartOf(part->str) < 0) throw std::runtime_error(where + ": unknown part '" + part->str + "' (year, month, day, hour, minute, second)");
       return;
    }
    if (fn != "concat") {

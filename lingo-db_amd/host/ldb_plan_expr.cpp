@@ -318,6 +318,31 @@ Scalar Interp::compileX(const std::vector<const ldb_table*>& sides, const J& e, 
    auto arity = [&](size_t n) {
       if (args.kind != J::ARR || args.arr.size() != n) throw std::runtime_error("plan: '" + op + "' takes " + std::to_string(n) + " arguments");
    };
+   if (op == "datediff") { // DateRuntime::dateDiffDay / Hour / Minute / Second (DateRuntime.cpp:83-98): (end - start) ns sdiv 10^9, then sdiv 60 / 3600 / 86400
+      arity(3);
+      if (args.arr[0].kind != J::STR) throw std::runtime_error("plan: 'datediff' takes [unit, end, start] with the unit as a string");
+      const int32_t unit = datepartOf(args.arr[0].str);
+      if (unit < LDB_DP_DAY) throw std::runtime_error("plan: 'datediff' unit '" + args.arr[0].str + "' (day, hour, minute, second)");
+      const int64_t perDay = unit == LDB_DP_DAY ? 1 : unit == LDB_DP_HOUR ? 24 : unit == LDB_DP_MINUTE ? 1440 : 86400;
+      const Scalar l = compileX(sides, args.arr[1], b), r = compileX(sides, args.arr[2], b);
+      if (l.kind != r.kind || (l.kind != Scalar::DATE && l.kind != Scalar::INT))
+         throw std::runtime_error(std::string("plan: 'datediff' over ") + scalarName(l) + " and " + scalarName(r) + ": two date32 values or two int64 ns values expected");
+      b.push(LDB_X_SUB);
+      if (l.kind == Scalar::DATE) { // whole days, multiplied out to the unit
+         if (perDay != 1) {
+            b.push(LDB_X_CONST, 0, {0, 0}, (__int128) perDay);
+            b.push(LDB_X_MUL);
+         }
+         return Scalar{};
+      }
+      b.push(LDB_X_CONST, 0, {0, 0}, (__int128) 1000000000);
+      b.push(LDB_X_SDIV); // truncating, as the reference's `/`
+      if (unit != LDB_DP_SECOND) {
+         b.push(LDB_X_CONST, 0, {0, 0}, (__int128) (86400 / perDay));
+         b.push(LDB_X_SDIV);
+      }
+      return Scalar{};
+   }
    if (op == "add" || op == "sub") {
       arity(2);
       XB lb, rb;

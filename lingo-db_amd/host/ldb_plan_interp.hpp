@@ -139,6 +139,7 @@ struct Interp {
    int64_t groupEstimate(const J& st, ldb_rel* in, bool hasKeys, bool* learn);
    // the `fn` forms of map: each returns the computed column
    ldb_table* mapExtractYear(const J& st, ldb_rel* in, const Sides& sides);
+   ldb_table* mapDatefn(const J& st, ldb_rel* in, const Sides& sides); // extract, date_trunc, add_months
    ldb_table* mapSubstr(const J& st, ldb_rel* in, const Sides& sides);
    ldb_table* mapCase(const J& st, ldb_rel* in, const Sides& sides); // upper, lower
    ldb_table* mapLength(const J& st, ldb_rel* in, const Sides& sides);
@@ -158,5 +159,6 @@ struct StepRow {
 const StepRow* findStep(const std::string& op); // nullptr: unknown step
 
 int32_t strcaseOf(const std::string& c); // "case" of a concat part
+int32_t datepartOf(const std::string& p); // "part" of extract / date_trunc and the unit of datediff as ldb_datepart, -1: unknown
 
 } // namespace ldbplan

@@ -13,6 +13,12 @@ int32_t strcaseOf(const std::string& c) {
    if (c == "lower") return LDB_SC_LOWER;
    throw std::runtime_error("plan: map concat: unknown case '" + c + "' (none, upper, lower)");
 }
+int32_t datepartOf(const std::string& p) {
+   static const char* const names[] = {"year", "month", "day", "hour", "minute", "second"}; // ldb_datepart
+   for (int32_t k = 0; k < 6; k++)
+      if (p == names[k]) return k;
+   return -1;
+}
 
 // ================================================================== environment
 // the named values (nullptr: all of them) and the hidden tables from index `hiddenFrom` on: hash tables first (they reference relations), then
@@ -476,6 +482,18 @@ ldb_table* Interp::mapExtractYear(const J& st, ldb_rel* in, const Sides& sides) 
    check(ldb_gpu_map_column(ctx, in, resolve(sides, st.s("col"), "map"), LDB_FN_EXTRACT_YEAR, st.s("as").c_str(), &t), "map extract_year");
    return t;
 }
+ldb_table* Interp::mapDatefn(const J& st, ldb_rel* in, const Sides& sides) { // Extract…FromDate / DateTrunc / DateAdd, DateSubtract (months)
+   const std::string& fn = st.s("fn");
+   const int32_t f = fn == "extract" ? LDB_DF_EXTRACT : fn == "date_trunc" ? LDB_DF_TRUNC : LDB_DF_ADD_MONTHS;
+   int32_t part = 0;
+   if (f != LDB_DF_ADD_MONTHS && (part = datepartOf(st.s("part"))) < 0) throw std::runtime_error("map " + fn + ": unknown part '" + st.s("part") + "'");
+   ldb_colref mc = {0, 0};
+   const bool perRow = f == LDB_DF_ADD_MONTHS && st.get("months_col");
+   if (perRow) mc = resolve(sides, st.s("months_col"), "map add_months");
+   ldb_table* t = nullptr;
+   check(ldb_gpu_map_datefn(ctx, in, resolve(sides, st.s("col"), "map"), f, part, f == LDB_DF_ADD_MONTHS && !perRow ? st.iOr("months", 0) : 0, perRow ? &mc : nullptr, st.s("as").c_str(), &t), ("map " + fn).c_str());
+   return t;
+}
 ldb_table* Interp::mapSubstr(const J& st, ldb_rel* in, const Sides& sides) {
    ldb_table* t = nullptr;
    check(ldb_gpu_map_substr(ctx, in, resolve(sides, st.s("col"), "map"), st.iOr("from", 1), st.iOr("for", 1 << 30), st.s("as").c_str(), &t), "map substr");
@@ -565,7 +583,8 @@ void Interp::stepMap(const J& st) { // subop.map: one computed column, attached 
       ldb_table* (Interp::*make)(const J&, ldb_rel*, const Sides&);
    } forms[] = {{"extract_year", &Interp::mapExtractYear}, {"substr", &Interp::mapSubstr},       {"upper", &Interp::mapCase},      {"lower", &Interp::mapCase},
                 {"length", &Interp::mapLength},            {"concat", &Interp::mapConcat},       {"to_varchar", &Interp::mapToVarchar},
-                {"to_int", &Interp::mapParse},             {"to_decimal", &Interp::mapParse},    {"to_date", &Interp::mapParse}};
+                {"to_int", &Interp::mapParse},             {"to_decimal", &Interp::mapParse},    {"to_date", &Interp::mapParse},
+                {"extract", &Interp::mapDatefn},           {"date_trunc", &Interp::mapDatefn},   {"add_months", &Interp::mapDatefn}};
    std::vector<const ldb_table*>* sides;
    ldb_rel* in = relOf(st.s("in"), &sides);
    (void) st.s("as");

@@ -10,7 +10,7 @@
 //
 //   get_external + scan                         → a base table relation; meta.filters → restrictions
 //   map                                         → column bindings (expressions are inlined into their consumers; runtime calls
-//                                                 ExtractYearFromDate / Substring / ToUpper / ToLower / StringLength → map fn, a Concatenate
+//                                                 ExtractYearFromDate / Extract{Month … Second}FromDate / DateTrunc / Substring / ToUpper / ToLower / StringLength → map fn, a Concatenate
 //                                                 nest → map fn concat with its parts, ConstLike → LIKE restrictions)
 //   filter all_true                             → restrictions (conjunctions, IN, LIKE, DNF → filter_dnf, anything else → a computed
 //                                                 boolean column + `= true`) / the conjuncts of a hash join (keys, residuals, post-join filters)
@@ -387,10 +387,17 @@ struct Translator {
       if (e->kind == Expr::COL) use(e->name);
       for (auto& a : e->args) useAll(a);
    }
+   // ExtractMonthFromDate … ExtractSecondFromDate → the part of an `extract` map step (the year keeps its own form, extract_year); nullptr: another call
+   static const char* datePartOfCall(const std::string& fn) {
+      static const std::pair<const char*, const char*> parts[] = {{"ExtractMonthFromDate", "month"}, {"ExtractDayFromDate", "day"}, {"ExtractHourFromDate", "hour"}, {"ExtractMinuteFromDate", "minute"}, {"ExtractSecondFromDate", "second"}};
+      for (auto& p : parts)
+         if (fn == p.first) return p.second;
+      return nullptr;
+   }
    // runtime calls nested inside an expression become columns first (the expression language is arithmetic / boolean only)
    ExprP materializeCalls(Stream& s, const ExprP& e, const std::string& hint) {
       if (e->kind != Expr::OP) return e;
-      if (e->name == "call" && (e->cmp == "ExtractYearFromDate" || e->cmp == "Substring" || e->cmp == "ToUpper" || e->cmp == "ToLower" || e->cmp == "StringLength" || e->cmp == "Concatenate")) return mk(Expr::COL, ensureCol(s, e, hint + "_f" + std::to_string(++nval)));
+      if (e->name == "call" && (e->cmp == "ExtractYearFromDate" || datePartOfCall(e->cmp) || e->cmp == "DateTrunc" || e->cmp == "Substring" || e->cmp == "ToUpper" || e->cmp == "ToLower" || e->cmp == "StringLength" || e->cmp == "Concatenate")) return mk(Expr::COL, ensureCol(s, e, hint + "_f" + std::to_string(++nval)));
       bool changed = false;
       std::vector<ExprP> args;
       for (auto& a : e->args) {
@@ -447,6 +454,17 @@ struct Translator {
             const std::string src = ensureCol(s, a0, hint + "_arg");
             flush(s);
             m.fields = {{"in", quote(s.rel)}, {"fn", "\"extract_year\""}, {"col", quote(src)}, {"as", quote(as)}};
+         } else if (datePartOfCall(e->cmp) && e->args.size() == 1) { // DateRuntime::extractMonth … extractSecond
+            const std::string src = ensureCol(s, a0, hint + "_arg");
+            flush(s);
+            m.fields = {{"in", quote(s.rel)}, {"fn", "\"extract\""}, {"part", quote(datePartOfCall(e->cmp))}, {"col", quote(src)}, {"as", quote(as)}};
+         } else if (e->cmp == "DateTrunc" && e->args.size() == 2) { // DateRuntime::dateTrunc(part, date): the part must be a constant the device form knows
+            if (a0->kind != Expr::CONST_STR) throw Unsupported("DateTrunc with a part that is not a string constant has no device form");
+            static const char* const known[] = {"year", "month", "day", "hour", "minute", "second"};
+            if (std::find_if(std::begin(known), std::end(known), [&](const char* k) { return a0->name == k; }) == std::end(known)) throw Unsupported("DateTrunc part '" + a0->name + "' has no device form");
+            const std::string src = ensureCol(s, stripCast(e->args[1]), hint + "_arg");
+            flush(s);
+            m.fields = {{"in", quote(s.rel)}, {"fn", "\"date_trunc\""}, {"part", quote(a0->name)}, {"col", quote(src)}, {"as", quote(as)}};
          } else if (e->cmp == "Substring" && e->args.size() == 3 && stripCast(e->args[1])->kind == Expr::CONST_INT && stripCast(e->args[2])->kind == Expr::CONST_INT) {
             const std::string src = ensureCol(s, a0, hint + "_arg"); // StringRuntime::substr(str, from, len)
             flush(s);

@@ -417,6 +417,15 @@ class Rel:
         check(self.ctx.lib.ldb_gpu_map_column(self.ctx.h, self.h, colref(*col), fn, name.encode(), C.byref(t)))
         return Table(self.ctx, t)
 
+    def map_datefn(self, col, fn, part=None, months=0, months_col=None, name="datefn"):
+        """date function of a date32 (days) or int64 (ns since the epoch) column as a new 1-column table: fn = capi.DF_EXTRACT
+        (part → int64) / DF_TRUNC (part → the input's type) / DF_ADD_MONTHS (`months`, or per row from `months_col`; no clamping
+        at the end of a month; NULL outside the type's range)"""
+        t = C.c_void_p()
+        mc = C.byref(colref(*months_col)) if months_col is not None else None
+        check(self.ctx.lib.ldb_gpu_map_datefn(self.ctx.h, self.h, colref(*col), fn, 0 if part is None else part, int(months), mc, name.encode(), C.byref(t)))
+        return Table(self.ctx, t)
+
     def map_muldiv(self, num, den, mul=1, mul_div_pow10=0, pow10=0, precision=38, scale=6, name="ratio"):
         """decimal `mul * num / den` per row as a new 1-column decimal128(precision, scale) table:
         ((num * mul) sdiv 10^mul_div_pow10) * 10^pow10 sdiv den in wrapping 128-bit arithmetic"""

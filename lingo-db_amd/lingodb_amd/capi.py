@@ -37,6 +37,9 @@ WIN_RANK, WIN_SUM, WIN_MIN, WIN_MAX, WIN_COUNT, WIN_COUNT_STAR = range(6)
 FRAME_UNBOUNDED_PRECEDING, FRAME_UNBOUNDED_FOLLOWING = -(2 ** 63), 2 ** 63 - 1
 # ldb_scalar_fn
 FN_EXTRACT_YEAR = 0
+# ldb_datefn / ldb_datepart (ldb_gpu_map_datefn)
+DF_EXTRACT, DF_TRUNC, DF_ADD_MONTHS = range(3)
+DP_YEAR, DP_MONTH, DP_DAY, DP_HOUR, DP_MINUTE, DP_SECOND = range(6)
 # ldb_strpart_kind / ldb_strcase (ldb_gpu_map_strcat)
 LDB_MAX_STRPARTS = 8
 STR_WHOLE = 2 ** 63 - 1
@@ -231,6 +234,7 @@ GPU_API = {
     "ldb_gpu_scan_count": (i32, [P, P, C.POINTER(FilterDesc), i32, C.POINTER(i64)]),
     "ldb_gpu_hash_keys": (i32, [P, P, C.POINTER(ColRef), i32, PP]),
     "ldb_gpu_map_column": (i32, [P, P, ColRef, i32, C.c_char_p, PP]),
+    "ldb_gpu_map_datefn": (i32, [P, P, ColRef, i32, i32, i64, C.POINTER(ColRef), C.c_char_p, PP]),
     "ldb_gpu_rel_zip": (i32, [P, P, P, PP]),
     "ldb_gpu_map_muldiv": (i32, [P, P, ColRef, i64, i64, i32, i32, ColRef, i32, i32, C.c_char_p, PP]),
     "ldb_gpu_groupby": (i32, [P, P, C.POINTER(FilterDesc), i32, C.POINTER(ColRef), i32, C.POINTER(AggSpec), i32, i64, PP]),
