@@ -754,15 +754,26 @@ int32_t ldb_gpu_join_probe_count(ldb_ctx* ctx, ldb_hashtable* ht, ldb_rel* probe
 typedef struct {
    ldb_colref col;
    int32_t descending;
-   int32_t reserved;
+   int32_t nulls; /* ldb_null_order: what a NULL in this key means */
 } ldb_sort_spec;
+/* LDB_NULLS_REFUSE: a key that holds a NULL (a cleared validity bit, or outer-join padding) gives LDB_ERR_UNSUPPORTED.
+ * LDB_NULLS_LARGEST: the reference's comparator over nullable operands (below).  Any other value: LDB_ERR_INVALID.
+ * (The reference's frontend has no NULLS FIRST / NULLS LAST clause, so there is no third order.) */
+typedef enum { LDB_NULLS_REFUSE = 0, LDB_NULLS_LARGEST = 1 } ldb_null_order;
 /* Replaces GrowingBuffer::sort / parallelSort (GrowingBuffer.cpp:54-78, Sorting.cpp:343-393)
  * with comparator semantics of db.sort_compare (LowerToStd.cpp:1046-1064).  Stable w.r.t. input
  * order among equal keys (the reference's std::sort leaves that order unspecified).
+ * NULLs: that lowering only sees non-nullable operands, because SimplifySortComparePattern
+ * (src/compiler/Dialect/DB/Transforms/PrepareLowering.cpp:106-132) has rewritten the nullable ones before it:
+ * left NULL and right not = +1, right NULL and left not = -1, both NULL = 0, otherwise db.sort_compare on the raw
+ * values; DESC swaps the operands (createSortedView, RelAlgToSubOp.cpp:1646-1653).  So with LDB_NULLS_LARGEST a
+ * NULL is the largest value of every type: it sorts LAST ascending and FIRST descending, and NULLs tie with each
+ * other, so the next key, then input order, decides between them.  The bytes stored under a NULL are never read.
+ * A key without any NULL is encoded the same whatever its `nulls` field says.
  * Float keys compare as db.cmp does (ordered compare): -0.0 and +0.0 are EQUAL keys, so the next
  * key, then input order, decides between them.  The order of NaN keys is unspecified (the
- * comparator is not an order on NaN).  1..8 keys; a utf8 key longer than 256 bytes, a key that
- * holds a NULL, or a ninth key gives LDB_ERR_UNSUPPORTED. */
+ * comparator is not an order on NaN).  1..8 keys; a utf8 key longer than 256 bytes (NULL rows do not
+ * count), a key with LDB_NULLS_REFUSE that holds a NULL, or a ninth key gives LDB_ERR_UNSUPPORTED. */
 int32_t ldb_gpu_sort(ldb_ctx* ctx, ldb_rel* in, const ldb_sort_spec* specs, int32_t n_specs, ldb_rel** out);
 /* Replaces Heap (Heap.cpp:8-72): first k rows of the sorted order. */
 int32_t ldb_gpu_topk(ldb_ctx* ctx, ldb_rel* in, const ldb_sort_spec* specs, int32_t n_specs, int64_t k, ldb_rel** out);

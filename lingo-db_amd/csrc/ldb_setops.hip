@@ -365,7 +365,9 @@ extern "C" int32_t ldb_gpu_window(ldb_ctx* ctx, ldb_rel* in, const ldb_colref* p
    // 1. the continuous view: rows ordered by (partition keys, ORDER BY keys) — the reference hash-partitions and sorts every
    //    partition's buffer; one sort with the partition keys in front yields the same per-partition order
    std::vector<ldb_sort_spec> specs;
-   for (int32_t k = 0; k < n_part; k++) specs.push_back({part_keys[k], 0, 0});
+   //    (a NULL partition key is a partition like any other, k_win_heads: it sorts as the largest value, so that partition comes last;
+   //    the ORDER BY keys keep the caller's `nulls`)
+   for (int32_t k = 0; k < n_part; k++) specs.push_back({part_keys[k], 0, LDB_NULLS_LARGEST});
    for (int32_t k = 0; k < n_order; k++) specs.push_back(order[k]);
    LdbRelHold sorted(ctx);
    if (!specs.empty()) {

@@ -2,6 +2,10 @@
 // Replaces (reference): GrowingBuffer::sort / parallelSort (src/runtime/GrowingBuffer.cpp:54-78,
 // src/runtime/Sorting.cpp:343-393) with the comparator of db.sort_compare
 // (src/compiler/Conversion/DBToStd/LowerToStd.cpp:1046-1064) and Heap (src/runtime/Heap.cpp:8-72).
+// NULLs: SimplifySortComparePattern (src/compiler/Dialect/DB/Transforms/PrepareLowering.cpp:106-132) rewrites the comparison of nullable
+// operands before that lowering — left NULL only: +1, right NULL only: -1, both: 0 — so NULL is the largest value of every type (last
+// ascending, first descending after createSortedView's operand swap, RelAlgToSubOp.cpp:1646-1653) and NULLs tie.  Here a key that
+// actually holds a NULL gets one flag byte in front of its value bytes (0 = value, 1 = NULL, value bytes of a NULL all zero).
 //
 // MI355X design: the CPU sorts row POINTERS through an indirect comparator call.  Here every row
 // gets an order-preserving fixed-width byte key (sign-flipped big-endian integers, zero-padded
@@ -64,8 +68,10 @@ struct DSortSpec {
    DCol col;
    int32_t descending;
    int32_t byte_off; // offset of this key inside the record
-   int32_t nbytes; // bytes this key occupies
+   int32_t nbytes; // value bytes of this key (it occupies null_flag + nbytes)
    int32_t str_pad; // utf8: padded string bytes (nbytes = str_pad + 4)
+   int32_t null_flag; // 1: one flag byte precedes the nbytes value bytes (LDB_NULLS_LARGEST and the key holds a NULL)
+   int32_t pad;
 };
 struct DSort {
    uint64_t n_rows;
@@ -89,6 +95,18 @@ __global__ void k_sort_keys(const DSort* __restrict__ d, uint64_t* __restrict__ 
          const uint8_t inv = sp.descending ? 0xFF : 0x00;
          uint32_t row = d_phys_row(sp.col, i);
          int b = sp.byte_off;
+         if (sp.null_flag) {
+            // NULL (validity bit clear or outer-join padding, row = LDB_NULL_ROW): the column is not loaded at all; flag 1, value bytes 0.
+            // Inverted like every other byte, so DESC puts the NULLs first and all NULLs of a key are one key value.
+            const bool ok = d_valid(sp.col, row);
+            d_put_byte(rec, b, (uint8_t) ((ok ? 0x00 : 0x01) ^ inv));
+            b++;
+            if (!ok) {
+               if (inv)
+                  for (int k = 0; k < sp.nbytes; k++) d_put_byte(rec, b + k, inv);
+               continue;
+            }
+         }
          if (sp.col.type == LDB_T_UTF8) {
             uint32_t len;
             const uint8_t* p = d_load_str(sp.col, row, &len);
@@ -113,15 +131,17 @@ __global__ void k_sort_keys(const DSort* __restrict__ d, uint64_t* __restrict__ 
 __global__ void k_str_maxlen(DCol col, uint64_t n, unsigned long long* out) {
    unsigned long long m = 0;
    for (uint64_t i = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x; i < n; i += (uint64_t) gridDim.x * blockDim.x) {
+      const uint32_t row = d_phys_row(col, i);
+      if (!d_valid(col, row)) continue; // NULL (padding has no row to read): takes no part in the pad length
       uint32_t len;
-      d_load_str(col, d_phys_row(col, i), &len);
+      d_load_str(col, row, &len);
       if (len > m) m = len;
    }
    if (m) atomicMax(out, m);
 }
-__global__ void k_all_valid(DCol col, uint64_t n, unsigned int* flag) {
+__global__ void k_all_valid(DCol col, uint64_t n, unsigned int* flag, unsigned int bit) {
    for (uint64_t i = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x; i < n; i += (uint64_t) gridDim.x * blockDim.x)
-      if (!d_valid(col, d_phys_row(col, i))) atomicOr(flag, 1u);
+      if (!d_valid(col, d_phys_row(col, i))) atomicOr(flag, bit);
 }
 
 // stable LSD sort of `perm` (n entries) by `words`-word records, digits [bit_lo, bit_hi) of each word
@@ -389,6 +409,8 @@ static int32_t sort_records(ldb_ctx* ctx, const uint64_t* keys, int words, uint6
 
 static int32_t sort_perm(ldb_ctx* ctx, ldb_rel* in, const ldb_sort_spec* specs, int32_t n_specs, uint64_t k, uint32_t** perm_out) {
    if (n_specs < 1 || n_specs > SORT_MAX_SPECS) LDB_FAIL(LDB_ERR_UNSUPPORTED, "sort: %d keys (1..%d supported)", n_specs, SORT_MAX_SPECS);
+   for (int s = 0; s < n_specs; s++)
+      if (specs[s].nulls != LDB_NULLS_REFUSE && specs[s].nulls != LDB_NULLS_LARGEST) LDB_FAIL(LDB_ERR_INVALID, "sort: key %d: unknown NULL order %d", s, specs[s].nulls);
    const uint64_t n = (uint64_t) in->n_rows;
    auto hp = std::make_unique<DSort>();
    DSort* h = hp.get();
@@ -396,7 +418,7 @@ static int32_t sort_perm(ldb_ctx* ctx, ldb_rel* in, const ldb_sort_spec* specs, 
    h->n_rows = n;
    h->n_specs = n_specs;
    const int grid = ldb_grid_for(ctx, (int64_t) n, 256, 8);
-   // pre-checks of all keys in one round trip: word 0 = "a key holds a NULL", word 1 + s = longest string of key s
+   // pre-checks of all keys in one round trip: bit s of word 0 = "key s holds a NULL", word 1 + s = longest string of key s
    unsigned long long* d_chk = nullptr;
    bool any_chk = false;
    for (int s = 0; s < n_specs; s++) {
@@ -409,8 +431,7 @@ static int32_t sort_perm(ldb_ctx* ctx, ldb_rel* in, const ldb_sort_spec* specs, 
             LDB_TRY(ldb_counters(ctx, 1 + SORT_MAX_SPECS, (uint64_t**) &d_chk)); // zeroed arena words
             any_chk = true;
          }
-         // db.sort_compare is only defined for non-nullable operands (LowerToStd.cpp:1050-1052)
-         if (sp.col.validity || padded) hipLaunchKernelGGL(k_all_valid, dim3(grid), dim3(256), 0, ctx->stream, sp.col, n, (unsigned int*) d_chk);
+         if (sp.col.validity || padded) hipLaunchKernelGGL(k_all_valid, dim3(grid), dim3(256), 0, ctx->stream, sp.col, n, (unsigned int*) d_chk, 1u << s);
          if (sp.col.type == LDB_T_UTF8) hipLaunchKernelGGL(k_str_maxlen, dim3(grid), dim3(256), 0, ctx->stream, sp.col, n, d_chk + 1 + s);
       }
    }
@@ -418,7 +439,11 @@ static int32_t sort_perm(ldb_ctx* ctx, ldb_rel* in, const ldb_sort_spec* specs, 
    if (any_chk) {
       LDB_HIP(hipGetLastError());
       LDB_TRY(LDB_READBACK(ctx, chk, d_chk, sizeof(chk)));
-      if (chk[0] & 1) LDB_FAIL(LDB_ERR_UNSUPPORTED, "sort: a key contains NULLs (nullable sort keys are not lowered to db.sort_compare)");
+      for (int s = 0; s < n_specs; s++) {
+         if (!((chk[0] >> s) & 1)) continue; // NULL-free: no flag byte, the record is what it is without LDB_NULLS_LARGEST
+         if (specs[s].nulls == LDB_NULLS_REFUSE) LDB_FAIL(LDB_ERR_UNSUPPORTED, "sort: a key contains NULLs (nullable sort keys are not lowered to db.sort_compare)");
+         h->specs[s].null_flag = 1;
+      }
    }
    int off = 0;
    for (int s = 0; s < n_specs; s++) {
@@ -434,7 +459,7 @@ static int32_t sort_perm(ldb_ctx* ctx, ldb_rel* in, const ldb_sort_spec* specs, 
       } else {
          sp.nbytes = 8;
       }
-      off += sp.nbytes;
+      off += sp.null_flag + sp.nbytes;
    }
    h->words = (off + 7) / 8;
    LdbBufs tmp(ctx);

@@ -175,10 +175,12 @@ std::vector<ldb_join_residual> Interp::residuals(const J& st, const Sides& probe
       for (auto& r : rs->arr) resid.push_back({resolve(probe, r.s("probe"), whatProbe), resolve(build, r.s("build"), whatBuild), opOf(r.s("op")), 0});
    return resid;
 }
-// "by" / "order_by": column names, or {"col", "desc"}
+// "by" / "order_by": column names, or {"col", "desc"}.  A plan states a reference query, and the reference's comparator is total over NULLs
+// (SimplifySortComparePattern, PrepareLowering.cpp:106-132): every key orders NULL as the largest value
 std::vector<ldb_sort_spec> Interp::sortSpecs(const Sides& sides, const J& by, const char* what) {
    std::vector<ldb_sort_spec> specs;
-   for (auto& b : by.arr) specs.push_back({resolve(sides, b.kind == J::STR ? b.str : b.s("col"), what), b.kind == J::OBJ && b.bOr("desc", false) ? 1 : 0, 0});
+   for (auto& b : by.arr)
+      specs.push_back({resolve(sides, b.kind == J::STR ? b.str : b.s("col"), what), b.kind == J::OBJ && b.bOr("desc", false) ? 1 : 0, LDB_NULLS_LARGEST});
    return specs;
 }
 // the {"col", "as"} entries of a column list name the columns of the table made from it

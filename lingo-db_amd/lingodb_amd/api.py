@@ -185,10 +185,11 @@ def str_minmax(fn, col):
     return agg(fn, col_expr(col), out_type=capi.T_UTF8)
 
 
-def sort_spec(col, descending=False):
+def sort_spec(col, descending=False, nulls=capi.NULLS_REFUSE):
     s = SortSpec()
     s.col = colref(*col)
     s.descending = 1 if descending else 0
+    s.nulls = int(nulls)
     return s
 
 

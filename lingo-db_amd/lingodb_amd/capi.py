@@ -104,7 +104,11 @@ class AggSpec(C.Structure):
 
 
 class SortSpec(C.Structure):
-    _fields_ = [("col", ColRef), ("descending", C.c_int32), ("reserved", C.c_int32)]
+    _fields_ = [("col", ColRef), ("descending", C.c_int32), ("nulls", C.c_int32)]
+
+
+# ldb_null_order: a key that holds a NULL is refused / NULL is the largest value (last ascending, first descending; NULLs tie)
+NULLS_REFUSE, NULLS_LARGEST = 0, 1
 
 
 class WindowFn(C.Structure):
