@@ -803,7 +803,9 @@ int32_t ldb_gpu_set_op(ldb_ctx* ctx, ldb_rel* left, const ldb_colref* left_cols,
  * empty).  LDB_WIN_RANK = entries between the frame begin and the current row + 1 (RankWindowFunc :2043-2058; row-number
  * semantics, as in the reference); SUM / MIN / MAX (NULL when the frame holds only NULLs) / COUNT (non-NULL values) /
  * COUNT_STAR over the frame.  Output: *out_rel = the input's rows in window order, *out_cols = one column per function
- * aligned with it (attach it with ldb_gpu_rel_zip).  Integer / decimal / date argument columns. */
+ * aligned with it (attach it with ldb_gpu_rel_zip).  Integer / decimal / date argument columns.  An inverted frame
+ * (frame_from > frame_to, where clamping does not bring the two ends together) is the empty state — SUM / MIN / MAX NULL,
+ * COUNT and COUNT_STAR 0 — where the reference's SegmentTreeView::lookup throws. */
 typedef enum { LDB_WIN_RANK = 0, LDB_WIN_SUM = 1, LDB_WIN_MIN = 2, LDB_WIN_MAX = 3, LDB_WIN_COUNT = 4, LDB_WIN_COUNT_STAR = 5 } ldb_window_fn_kind;
 typedef struct {
    int32_t fn; /* ldb_window_fn_kind */
