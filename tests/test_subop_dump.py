@@ -530,3 +530,22 @@ def test_mutated_dumps_never_crash_the_consumer():
                 assert e.status in (capi.LDB_ERR_INVALID, capi.LDB_ERR_UNSUPPORTED)
                 outcomes["err"] += 1
     assert outcomes["err"] > 100 and outcomes["ok"] > 20, outcomes
+
+
+with open(os.path.join(GOLD, "translated_subop.json")) as _f:
+    TRANSLATED = json.load(_f)  # tests/golden/make_subop_translated.py: {dump file stem: {"status", "plan", "report"}}
+
+
+def test_every_dump_has_its_recorded_translation():
+    assert sorted(TRANSLATED) == sorted(n[:-5] for n in os.listdir(GOLD) if n.startswith("subop_") and n.endswith(".json")) and len(TRANSLATED) == 40
+
+
+@pytest.mark.parametrize("stem", sorted(TRANSLATED))
+def test_translation_is_the_recorded_text(stem):
+    """the plan text and the placement report of every committed dump, byte for byte (value names, field order and spacing included):
+    a change to the translator that is not meant to change what it writes leaves them alone"""
+    want = TRANSLATED[stem]
+    with open(os.path.join(GOLD, stem + ".json")) as f:
+        text, _ = api.translate_subop_dump(f.read(), stem[len("subop_"):])
+    assert want["status"] == capi.LDB_OK and text == want["plan"]
+    assert capi.host_lib().ldb_subop_report().decode() == want["report"]
